@@ -14,18 +14,26 @@ SGD → all-gather, overlapped with backward; the reference's ``DistriOptimizerP
 ``DL/models/utils/DistriOptimizerPerf.scala:32-146``).  Weak scaling: per-GPU batch fixed (default
 256), global batch = 256·N.  The timed region is exactly K full training steps (forward, criterion,
 backward, gradient sync, optimizer update) bracketed by barrier + device synchronize; the MAX
-elapsed over ranks is reported.  Rank 0 prints one JSON line.  After the timed region a few extra
-steps run with per-phase HIP-event timers to report the mean "aggregate gradient" (reduce-scatter
-wait), "compute weight" (shard update) and "send weights" (all-gather wait) times — outside the
-timed region, so the timers cannot perturb the headline number.
+elapsed over ranks is reported.  Rank 0 prints one JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  ``--dump-outputs DIR``
+also writes what the last timed step computed (see ``_dump_outputs``) so two builds can be compared
+output for output: the inputs are seeded, identical from run to run for the same arguments, and with
+this option the last timed step starts again from the seeded initial weights (the clock is stopped
+while they are put back; see ``_timed``), so its outputs do not depend on the steps before it.
+
+``--full`` adds the secondary measurements, each in runs of its own after the timed region so they
+cannot perturb the headline number: a few extra steps with per-phase HIP-event timers that report
+the mean "aggregate gradient" (reduce-scatter wait), "compute weight" (shard update) and "send
+weights" (all-gather wait) times (``--phase-steps``), and the fp32 record below (``--fp32-steps``).
 
 The model, criterion and optimizer are built exactly as the reference's ImageNet ResNet-50
 training (``DL/models/resnet/{ResNet,TrainImageNet,Utils}.scala``): convs with bias and
 L2Regularizer(1e-4), BN eps 1e-3, SGD(lr 0.1, momentum 0.9, dampening 0, nesterov, wd 1e-4).
 
-The same invocation then times the identical config at the reference's precision — fp32 compute
-(bf16x3 operand splits on the matrix cores, fp32 accumulation; ``--fp32-steps``, default 10 on GPU)
-— and reports it as ``"fp32": {"value", "ms_per_step", ...}`` next to the bf16 headline ``value``.
+With ``--full`` the same invocation then times the identical config at the reference's precision —
+fp32 compute (bf16x3 operand splits on the matrix cores, fp32 accumulation; ``--fp32-steps``, default
+10 on GPU) — and reports it as ``"fp32": {"value", "ms_per_step", ...}`` next to the bf16 headline ``value``.
 
 ``--device cpu`` (gloo, fp32) with ``--batch`` / ``--image-size`` exists to exercise the
 multi-rank launch path on a host without GPUs (tests/test_bench_launch.py).
@@ -61,15 +69,22 @@ def _parse(argv=None):
                     help="gradient wire format (fp32 | bf16 | bf16_truncate); default bf16_truncate for "
                          "N > 1 — the reference's FP16CompressedTensor bit format "
                          "(DL/parameters/FP16CompressedTensor.scala:271-277) — and fp32 at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the headline: the per-phase timers "
+                         "(--phase-steps) and the fp32 record (--fp32-steps); off in a plain run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/loss.npy (float32); "
+                         "that step then starts from the seeded initial weights, so the file is "
+                         "comparable from run to run")
     ap.add_argument("--phase-steps", type=int, default=3,
-                    help="extra untimed steps with per-phase timers (0 = off)")
+                    help="with --full: extra untimed steps with per-phase timers (0 = off)")
     ap.add_argument("--syncbn", action="store_true",
                     help="cross-rank SyncBN in every BN (setParallism), the reference's TrainImageNet option")
     ap.add_argument("--force-distri", action="store_true",
                     help="use the DistriOptimizer (RCCL path) even at world size 1 (path validation)")
     ap.add_argument("--fp32-steps", type=int, default=None,
-                    help="also time this many steps of the same config in fp32 compute (the reference's "
-                         "precision; bf16x3 on the matrix cores) after the bf16 headline, reported as "
+                    help="with --full: also time this many steps of the same config in fp32 compute (the "
+                         "reference's precision; bf16x3 on the matrix cores) after the bf16 headline, reported as "
                          "\"fp32\" in the JSON line (default 5 on GPU, 0 on CPU; 0 = off)")
     ap.add_argument("--fp32-warmup", type=int, default=2)
     return ap.parse_args(argv)
@@ -133,10 +148,43 @@ def _build(args, dev, rank):
     return model, crit, sgd, batches
 
 
-def _timed(args, dev, rank, distri, warmup, steps):
+def _snapshot(opt):
+    """The seeded state a step starts from: master weights and the modules' non-trainable buffers
+    (BN running statistics), cloned right after ``prepare()``."""
+    return (opt.flat.weight.detach().clone(),
+            [t.detach().clone() for t in (opt.model.getExtraParameter() or [])])
+
+
+def _rewind(opt, snap):
+    """Put the optimizer back on the snapshot: weights (and their compute-dtype shadow), buffers,
+    and a zero momentum buffer — v = m·0 + g is the first-iteration rule, so the next step is the
+    step a fresh optimizer would take, with the kernels the compile phase pinned."""
+    import torch
+    w0, extra0 = snap
+    opt.flat.weight.copy_(w0)
+    if opt.flat.shadow is not None:
+        opt.flat.refresh_shadow()
+    for t, t0 in zip(opt.model.getExtraParameter() or [], extra0):
+        t.copy_(t0)
+    for meth in opt.optim_methods.values():
+        buf = meth.state.get("dfdx")
+        if isinstance(buf, torch.Tensor):
+            buf.zero_()
+
+
+def _timed(args, dev, rank, distri, warmup, steps, rewind_last=False):
     """Build the model / optimizer at the current compute dtype, run ``warmup`` untimed steps (the
     first is the training compile phase), then time exactly ``steps`` steps bracketed by barrier +
-    device synchronize; returns (optimizer, batches, max elapsed over ranks, final loss, sync)."""
+    device synchronize; returns (optimizer, batches, max elapsed over ranks, final loss, sync).
+
+    ``rewind_last`` (``--dump-outputs``, LocalOptimizer): the clock stops before the last timed step,
+    the optimizer is put back on its seeded initial state (``_rewind``) and the clock resumes, so
+    what that step computes depends on the seeded inputs alone and not on the steps before it.  The
+    step is not bit reproducible on a GPU (kernels are chosen by timing in the first step; BN
+    statistics and split-K sums use float atomics) and at lr 0.1 without a warm-up on random labels
+    training amplifies that rounding from step to step — two runs of one build differ by 1e-5
+    relative in the loss after one step, 6 % after 25 — so only a step from a fixed state can be
+    compared between runs or builds to within rounding."""
     import torch
     from bigdl.optim.optimizer import LocalOptimizer
     from bigdl.parallel import comm
@@ -148,6 +196,7 @@ def _timed(args, dev, rank, distri, warmup, steps):
     else:
         opt = LocalOptimizer(model, [batches[0]], crit, sgd, batch_size=B)
     opt.prepare()
+    snap = _snapshot(opt) if rewind_last and type(opt) is LocalOptimizer else None
 
     def sync():
         if hasattr(opt, "_wait_all_gathers"):
@@ -163,12 +212,33 @@ def _timed(args, dev, rank, distri, warmup, steps):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     loss = None
+    paused = 0.0
     for i in range(steps):
+        if snap is not None and i == steps - 1:
+            sync()
+            tp = time.perf_counter()
+            _rewind(opt, snap)
+            sync()
+            paused = time.perf_counter() - tp
         loss = opt.train_step(batches[i % 2])
     sync()
     comm.barrier()
-    elapsed = comm.allreduce_max(time.perf_counter() - t0)
+    elapsed = comm.allreduce_max(time.perf_counter() - t0 - paused)
     return opt, batches, elapsed, (float(loss) if loss is not None else float("nan")), sync
+
+
+def _dump_outputs(out_dir, final_loss):
+    """Write what a caller of the timed path receives from the last timed step: ``loss.npy``, the
+    value ``train_step`` returned, float32 [1].  The inputs and the initial weights are seeded and
+    that step starts from them (``_timed``, ``rewind_last``): on the CPU two runs write identical
+    files; on an MI355X two runs of one build differ by 1.4e-4 – 2.2e-4 relative (three pairs; a
+    step further from the seeded state it is 8e-4, two steps further 1.8e-3).
+    The step's logits and updated weights are not written: one bf16 forward / backward through the
+    53 randomly initialised conv + BN layers already spreads them by 4 % / 3 % (relative L2)
+    between two runs of one build, too much to tell two builds apart."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([final_loss], dtype=np.float32))
 
 
 def main(argv=None):
@@ -202,11 +272,15 @@ def main(argv=None):
 
     from bigdl.parallel import comm
     B = args.batch
-    opt, batches, elapsed, final_loss, sync = _timed(args, dev, rank, distri, args.warmup, args.steps)
+    opt, batches, elapsed, final_loss, sync = _timed(args, dev, rank, distri, args.warmup, args.steps,
+                                                     rewind_last=bool(args.dump_outputs))
 
-    # per-phase means over a few extra (untimed) steps: HIP-event timers on the step stream
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, final_loss)
+
+    # --full: per-phase means over a few extra (untimed) steps: HIP-event timers on the step stream
     phases = {}
-    if args.phase_steps > 0:
+    if args.full and args.phase_steps > 0:
         tr = opt.tracer
         tr.enabled = True
         tr.device = dev.type == "cuda"
@@ -228,12 +302,12 @@ def main(argv=None):
     ms = elapsed / args.steps * 1e3
     imgs = B * world * args.steps / elapsed
 
-    # the same config at the reference's precision (fp32 compute: bf16x3 splits on the matrix cores,
-    # tests/test_fp32x3.py), timed the same way after the bf16 headline
+    # --full: the same config at the reference's precision (fp32 compute: bf16x3 splits on the matrix
+    # cores, tests/test_fp32x3.py), timed the same way after the bf16 headline
     fp32 = None
     n32 = args.fp32_steps if args.fp32_steps is not None else (10 if dev.type == "cuda" else 0)
     driver = type(opt).__name__
-    if n32 > 0 and dtype != "fp32":
+    if args.full and n32 > 0 and dtype != "fp32":
         del opt, batches
         if dev.type == "cuda":
             torch.cuda.empty_cache()

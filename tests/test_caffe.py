@@ -1,6 +1,6 @@
 """Caffe import/export (reference: TS/utils/CaffeLoaderSpec.scala, CaffePersisterSpec.scala,
 pyspark/test/bigdl/caffe/test_load_caffe.py).  Fixtures: the reference's own test.prototxt /
-test.caffemodel (parsed with our re-declared caffe.proto; plain protobuf, nothing executed)."""
+test.caffemodel, stored under tests/golden/caffe (parsed with our re-declared caffe.proto; plain protobuf, nothing executed)."""
 import os
 
 import pytest
@@ -12,9 +12,8 @@ from bigdl.nn import (Graph, Input, JoinTable, Linear, ReLU, Sequential, SoftMax
 from bigdl.serialization.caffe_loader import CaffeLoader, CaffeConversionException, Customizable, load_caffe_model
 from bigdl.serialization.caffe_persister import CaffePersister
 
-RES = "/root/reference/spark/dl/src/test/resources/caffe"
+RES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "caffe")
 PROTO, MODEL = os.path.join(RES, "test.prototxt"), os.path.join(RES, "test.caffemodel")
-have_fixtures = pytest.mark.skipif(not os.path.exists(MODEL), reason="reference caffe fixtures not present")
 
 CONV1_HEAD = [0.4156779647, 0.3547672033, 0.1817495823, -0.1393318474, 0.4004031420, 0.0634599924]
 CONV1_BIAS = [0.0458712392, -0.0029324144, -0.0251041390, 0.0052924110]
@@ -28,7 +27,6 @@ def _small():
             .add(Linear(27, 2, with_bias=False).set_name("ip")))
 
 
-@have_fixtures
 def test_load_weights_match_all():
     m = CaffeLoader.load(_small(), PROTO, MODEL)
     p = m.getParametersTable()
@@ -39,7 +37,6 @@ def test_load_weights_match_all():
     torch.testing.assert_close(p["ip"]["weight"].reshape(-1)[:4], torch.tensor(IP_HEAD), atol=1e-6, rtol=0)
 
 
-@have_fixtures
 def test_load_weights_partial():
     m = _small()
     m.modules[1].set_name("conv3")
@@ -51,7 +48,6 @@ def test_load_weights_partial():
     torch.testing.assert_close(m.modules[0].bias, torch.tensor(CONV1_BIAS), atol=1e-6, rtol=0)
 
 
-@have_fixtures
 def test_load_caffe_dynamic_and_customized():
     from bigdl.nn import Identity
     from bigdl.nn.graph import ModuleNode

@@ -1,5 +1,5 @@
-"""Torch7 .t7 reader/writer (TorchFile.scala): real fixtures from the reference's test resources
-and module round trips (forward equality after save → load)."""
+"""Torch7 .t7 reader/writer (TorchFile.scala): a real fixture from the reference's test resources
+(stored under tests/golden/torch) and module round trips (forward equality after save → load)."""
 import os
 
 import numpy as np
@@ -11,10 +11,9 @@ from bigdl.nn.module import Module
 from bigdl.serialization.torch_file import load_torch_file, save_torch_file
 from bigdl.utils.table import Table
 
-FIX = "/root/reference/spark/dl/src/test/resources/torch"
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "torch")
 
 
-@pytest.mark.skipif(not os.path.isdir(FIX), reason="reference fixtures not mounted")
 def test_reads_reference_tensor_fixture():
     t = load_torch_file(os.path.join(FIX, "n02110063_11239.t7"))
     assert isinstance(t, torch.Tensor) and t.shape == (3, 224, 224) and t.dtype == torch.float32
