@@ -202,7 +202,9 @@ __global__ void __launch_bounds__(64 * WM * WN, NS == 2 ? (BM * BN <= 128 * 64 ?
   int rbase[GB];  // fp32 elements
   uint64_t vmask[GB];
   int c4h[C4 ? GB : 1], c4w[C4 ? GB : 1], c4t[C4 ? GB : 1];  // C4: the row's window origin, its lane's tap
-  const bool pw_direct = PW && p.sh == 1 && p.sw == 1;
+  // rows read in place only when the output grid IS the input grid: a sub-pixel data-gradient class can
+  // ask for more output rows / columns than dY has (input pixels past the last window), which must read 0
+  const bool pw_direct = PW && p.sh == 1 && p.sw == 1 && p.P == p.H && p.Q == p.W;
 #pragma unroll
   for (int j = 0; j < GB; ++j) {
     const int row = 8 * (wid + NW * j) + lrow;
@@ -240,7 +242,7 @@ __global__ void __launch_bounds__(64 * WM * WN, NS == 2 ? (BM * BN <= 128 * 64 ?
     rbase[j] = (img + h * p.W + w) * p.ldx + chunk * 4;
     uint64_t msk = 0;
     if (PW) {
-      msk = img >= 0 ? 1ull : 0ull;
+      msk = (img >= 0 && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W) ? 1ull : 0ull;
     } else if (img >= 0) {
       for (int r = 0; r < p.R; ++r) {
         const int hh = h + r * p.dh;

@@ -889,11 +889,16 @@ def conv_backward(gy, x, w4, stride, pad, dilation=(1, 1), groups=1, need_input=
         # each half independently on the direct kernels when its shape allows, else on the split path.
         # The one-launch fp32 weight gradient is forked onto the wgrad side stream BEFORE the data
         # gradient (as the bf16 path does, native_ops.conv2d_backward), so it runs beside the
-        # backward-data chain; the optimizer joins the side stream before the update.
+        # backward-data chain; the optimizer joins the side stream before the update.  Only when the
+        # data gradient is sure to be computed here: a NotImplemented after the fork would hand the
+        # caller's fallback accumulators that already hold this gradient (it would be added twice).
         wg_done = False
         if gw_acc is not None and scale != 0 and _direct_wgrad_ok(x, gy, gw_acc):
             from .native_ops import _wgrad_side_stream
             side = _wgrad_side_stream(gy)
+            if side is not None and need_input and _split_dgrad_plan(gy, w4, tuple(x.shape), stride, pad,
+                                                                     dilation) is None:
+                side = None  # (the weight gradient runs after the data gradient, if there is one)
             if side is not None:
                 with torch.cuda.stream(side):
                     _direct_wgrad(x, gy, gw_acc, scale, stride, pad, dilation, pro=pro)
@@ -931,6 +936,33 @@ def conv_backward(gy, x, w4, stride, pad, dilation=(1, 1), groups=1, need_input=
 
 
 
+def _split_dgrad_plan(gy, w4, x_shape, stride, pad, dilation):
+    """The split-operand data gradient's geometry — (hl, wl, pd, npart, nbc): the dY lattice, the
+    stride-1 conv's padding, the split's parts and the images per launch — or None when it refuses the
+    shape.  It is the last resort of every fp32 data gradient, so ``conv_backward`` asks it BEFORE it
+    forks the weight gradient: a call that will end in NotImplemented must not have written gw / gb."""
+    nb, c, h, w = x_shape
+    k, _, r, s = w4.shape
+    p, q = gy.shape[2], gy.shape[3]
+    kp, cq = _r(k, 8), _r(c, 4)
+    hl, wl = h + 2 * pad[0] - dilation[0] * (r - 1), w + 2 * pad[1] - dilation[1] * (s - 1)
+    pd = (dilation[0] * (r - 1) - pad[0], dilation[1] * (s - 1) - pad[1])
+    npart = 2 if _two_part() else 3
+    if hl <= 0 or wl <= 0 or pd[0] < 0 or pd[1] < 0 or not _fits(hl * wl * npart * kp * 2, cq * r * s * 3 * kp * 2):
+        return None
+    if tuple(stride) == (1, 1) and (hl, wl) != (p, q):
+        return None
+    # images per launch: the dY operand must stay below the kernels' 2 GiB buffer offsets (the
+    # 224² stem's lattice at batch 256 does not), so large batches run in image chunks
+    nbc = min(nb, _OPERAND_LIMIT // (hl * wl * npart * kp * 2))
+    if nbc < nb and cq <= 4:
+        # the RGB stem at ImageNet batch sizes: a 4-channel data gradient leaves the MFMA tiles almost
+        # idle and the lattice + splits cost more than torch's fp32 kernel (measured 1.8 vs 0.9 ms/step
+        # for data + weight gradient, profiles/r4_fp32_profile.txt), so that one conv stays on torch
+        return None
+    return hl, wl, pd, npart, nbc
+
+
 def _split_backward(gy, x, w4, stride, pad, dilation, need_input, gw_acc, scale, slot, residual=None, bn_fuse=None):
     return _split_backward_full(gy, x, w4, stride, pad, dilation, need_input, gw_acc, None, scale, residual, slot,
                                 bn_fuse)
@@ -950,22 +982,11 @@ def _split_backward_full(gy, x, w4, stride, pad, dilation, need_input, gw_acc, g
     two = _two_part()
     g3 = None
     if need_input:
-        hl, wl = h + 2 * pad[0] - dilation[0] * (r - 1), w + 2 * pad[1] - dilation[1] * (s - 1)
-        pd = (dilation[0] * (r - 1) - pad[0], dilation[1] * (s - 1) - pad[1])
-        npart = 2 if two else 3
-        if pd[0] < 0 or pd[1] < 0 or not _fits(hl * wl * npart * kp * 2, cq * r * s * 3 * kp * 2):
+        plan = _split_dgrad_plan(gy, w4, (nb, c, h, w), stride, pad, dilation)
+        if plan is None:
             return NotImplemented
+        hl, wl, pd, npart, nbc = plan
         strided = tuple(stride) != (1, 1)
-        if not strided and (hl, wl) != (p, q):
-            return NotImplemented
-        # images per launch: the dY operand must stay below the kernels' 2 GiB buffer offsets (the
-        # 224² stem's lattice at batch 256 does not), so large batches run in image chunks
-        nbc = min(nb, _OPERAND_LIMIT // (hl * wl * npart * kp * 2))
-        if nbc < nb and cq <= 4:
-            # the RGB stem at ImageNet batch sizes: a 4-channel data gradient leaves the MFMA tiles almost
-            # idle and the lattice + splits cost more than torch's fp32 kernel (measured 1.8 vs 0.9 ms/step
-            # for data + weight gradient, profiles/r4_fp32_profile.txt), so that one conv stays on torch
-            return NotImplemented
         wt = w4.detach().float().flip(2, 3).permute(1, 2, 3, 0).reshape(c * r * s, k)  # [C][R][S][K]
         wt3 = torch.zeros((cq * r * s, 3 * kp), dtype=_bf16, device=x.device) if cq != c else None
         wt3 = split(wt, kp, HLH, False, out=wt3)
