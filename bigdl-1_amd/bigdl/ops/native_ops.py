@@ -17,6 +17,7 @@ from . import reference as R_
 from . import fp32x3 as F3
 from ..utils import config
 from .native import register, ptr, stream_ptr, check
+from .lars_table import LarsTable
 
 _bf16 = torch.bfloat16
 _f32 = torch.float32
@@ -1726,6 +1727,57 @@ def sgd_step(w, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_s
     check(fn(ptr(w), ptr(g), ptr(buf if momentum != 0 else None), ptr(shadow), ptr(lrs), ptr(wds),
              _ll(n), _f(lr), _f(momentum), _f(dampening), _f(weight_decay), C.c_int(int(bool(nesterov))),
              C.c_int(int(bool(first_step))), _f(grad_scale), ptr(first_dev), _s()), "sgd")
+    return w
+
+
+def _lars_table_ok(table, w):
+    return (isinstance(table, LarsTable) and table.device == w.device and w.numel() == table.n
+            and hasattr(_lib(), "bigdl_lars_sgd"))
+
+
+def _lars_g_ok(g, n):
+    g16 = g.dtype == _bf16
+    return (g.dtype in (_f32, _bf16) and g.is_cuda and g.is_contiguous() and g.numel() == n
+            and g.data_ptr() % (8 if g16 else 16) == 0)
+
+
+@register("lars_sumsq")
+def lars_sumsq(w, g, table, sums=None):
+    """Per-layer (Σw², Σg²) of the owned pieces of ``table`` (bigdl_lars_sumsq + bigdl_lars_fold:
+    one partial per chunk, then one fixed-order sum per layer; no float atomics).  ``g`` is fp32 or
+    the bf16 wire shard.  Returns fp32 ``[2·L]`` (``sums`` when given)."""
+    if not _lars_table_ok(table, w) or w.dtype != _f32 or not _vec_ok(w, n=table.n) or not _lars_g_ok(g, table.n):
+        return NotImplemented
+    if sums is None:
+        sums = torch.empty(2 * table.n_layers, dtype=_f32, device=w.device)
+    elif not (sums.is_cuda and sums.dtype == _f32 and sums.is_contiguous() and sums.numel() == 2 * table.n_layers):
+        return NotImplemented
+    check(_lib().bigdl_lars_sumsq(ptr(w), ptr(g), C.c_int(int(g.dtype == _bf16)), ptr(table.cstart), ptr(table.clen),
+                                  C.c_int(table.n_chunks), ptr(table.partials), _s()), "lars_sumsq")
+    check(_lib().bigdl_lars_fold(ptr(table.partials), ptr(table.lptr), ptr(table.lchunks), C.c_int(table.n_layers),
+                                 ptr(sums), _s()), "lars_fold")
+    return sums
+
+
+@register("lars_step")
+def lars_step(w, g, v, table, sums, hyper, grad_scale=1.0, shadow=None, c0=0, c1=None):
+    """LARS momentum update of chunks ``[c0, c1)`` of ``table`` (bigdl_lars_sgd); the layer sums and
+    the ``[L, 4]`` hyper-parameter rows are read on the device."""
+    F3.mark_dirty(w)
+    c1 = getattr(table, "n_chunks", 0) if c1 is None else c1
+    if not _lars_table_ok(table, w) or w.dtype != _f32 or not _vec_ok(w, v, n=table.n) or v.dtype != _f32:
+        return NotImplemented
+    if not _lars_g_ok(g, table.n) or not 0 <= c0 <= c1 <= table.n_chunks:
+        return NotImplemented
+    for t, m in ((sums, 2 * table.n_layers), (hyper, 4 * table.n_layers)):
+        if not (t.is_cuda and t.dtype == _f32 and t.is_contiguous() and t.numel() == m):
+            return NotImplemented
+    if shadow is not None and not (shadow.is_cuda and shadow.dtype == _bf16 and shadow.is_contiguous()
+                                   and shadow.numel() == table.n and shadow.data_ptr() % 8 == 0):
+        return NotImplemented
+    check(_lib().bigdl_lars_sgd(ptr(w), ptr(g), C.c_int(int(g.dtype == _bf16)), ptr(v), ptr(shadow), ptr(table.cstart),
+                                ptr(table.clen), ptr(table.clayer), ptr(sums), ptr(hyper), C.c_int(c0), C.c_int(c1),
+                                _f(grad_scale), _s()), "lars_sgd")
     return w
 
 

@@ -559,6 +559,44 @@ def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_sc
     return w
 
 
+def lars_sumsq(w, g, table, sums=None):
+    """Per-layer (Σw², Σg²) over the owned pieces of ``table``: fp32 ``[2·L]``, layer ``l`` at
+    ``[2l, 2l+1]``; a layer with no piece gives exactly 0.  ``g`` is fp32 or the bf16 wire shard.
+    Tensor ops only (no host read); accumulated in fp64 so the result is the rounded exact sum."""
+    idx, lay = table.elements()
+    acc = torch.zeros(table.n_layers, 2, dtype=torch.float64, device=w.device)
+    acc[:, 0].index_add_(0, lay, w[idx].double().square())
+    acc[:, 1].index_add_(0, lay, g[idx].double().square())
+    out = acc.reshape(-1).float()
+    if sums is None:
+        return out
+    return sums.copy_(out)
+
+
+def lars_step(w, g, v, table, sums, hyper, grad_scale=1.0, shadow=None, c0=0, c1=None):
+    """LARS momentum update of chunks ``[c0, c1)`` of ``table`` (``LarsSGD.optimize``'s rule, per
+    layer, from the all-reduced ``sums`` and the ``[L, 4]`` rows ``(lr·trust, weightDecay, momentum,
+    lr)`` of ``hyper``, both on the device): wn = √Σw², gn = grad_scale·√Σg²; rate = lr·trust·wn /
+    (gn + wd·wn + 1e-12) when both norms are positive, else lr; v = mom·v + rate·(g·grad_scale +
+    wd·w); w -= v; shadow = bf16(w).  Tensor ops only (no host read)."""
+    idx, lay = table.elements(c0, c1)
+    s = sums.reshape(-1, 2).float()
+    h = hyper.reshape(-1, 4).float()
+    wn = s[:, 0].sqrt()
+    gn = s[:, 1].sqrt() * grad_scale
+    wd, mom = h[:, 1], h[:, 2]
+    rate = torch.where((wn > 0) & (gn > 0), h[:, 0] * (wn / (gn + wd * wn + 1e-12)), h[:, 3])
+    wv = w[idx]
+    upd = (g[idx].float() * grad_scale + wd[lay] * wv) * rate[lay]
+    nv = v[idx] * mom[lay] + upd
+    nw = wv - nv
+    v[idx] = nv
+    w[idx] = nw
+    if shadow is not None:
+        shadow[idx] = nw.to(shadow.dtype)
+    return w
+
+
 # ------------------------------------------------------------------------- recurrent
 def lstm_cell_forward(xg, hg, c_prev, h_out=None, c_out=None, act_out=None, tc_out=None):
     """Pointwise LSTM cell (``DL/nn/LSTM.scala:124-187``), gate order (i, g, f, o) along the

@@ -773,16 +773,84 @@ class LBFGS(OptimMethod):
 
 class LarsSGD(SGD):
     """Layer-wise adaptive rate scaling (``LarsSGD.scala:47``): per-layer trust ratio
-    ‖w‖ / (‖g‖ + wd·‖w‖) × trust, computed per parameter slice.  The ratio needs whole-layer norms, so
-    the DistriOptimizer runs it replicated (a rank's shard can split a layer)."""
+    ‖w‖ / (‖g‖ + wd·‖w‖) × trust, computed per parameter slice.
+
+    One method is one layer (or the layers listed in ``slices``); :meth:`createOptimForModule`
+    builds the usual per-module dict.  ``optimize`` is the serial form: a loop over the layers with
+    two host reads of the norms per layer.  The optimizers group every ``LarsSGD`` they hold into a
+    :class:`bigdl.optim.lars.LarsPlan` instead — always in the DistriOptimizer's sharded mode, and
+    whenever the weights are on the GPU (``bigdl.lars.fused``): per-layer (Σw², Σg²) by two small
+    kernels, one all-reduce of 2·L floats, then one fused update per owned range, with no host
+    synchronisation and one momentum buffer for all layers (``supports_layer_shards``).  The plain
+    slice protocol (``supports_slices``) stays off: a slice alone cannot know its layer's norm."""
 
     supports_slices = False
+    #: the DistriOptimizer may run this method sharded through a LarsPlan
+    supports_layer_shards = True
 
     def __init__(self, lr_schedule=None, learningrate=1e-3, learningrate_decay=0.01, weightdecay=5e-4,
                  momentum=0.5, trust=1.0, bigdl_type="float"):
         super().__init__(learningrate, learningrate_decay, weightdecay, momentum, leaningrate_schedule=lr_schedule)
         self.trust = trust
         self.slices = None  # list of (offset, length) set by the optimizer driver
+        #: several methods may share one schedule; only its owner reports the rate
+        self.lrScheduleOwner = True
+
+    def prepare_graph(self) -> bool:
+        return False  # HIP-graph capture of LARS is not supported
+
+    def getHyperParameter(self) -> str:
+        return super().getHyperParameter() if getattr(self, "lrScheduleOwner", True) else ""
+
+    # ---- per-module construction (LarsSGD.scala:163-282) ---------------------------------------
+    @staticmethod
+    def _leaf_modules(model):
+        """Leaf modules that hold parameters, recursing through containers, in execution order."""
+        kids = model.children() if hasattr(model, "children") else []
+        if kids:
+            out = []
+            for k in kids:
+                if k.parameters() is not None:
+                    out.extend(LarsSGD._leaf_modules(k))
+            return out
+        p = model.parameters()
+        return [model] if p is not None and p[0] else []
+
+    @staticmethod
+    def createOptimLRSchedulerForModule(model, lrScheGenerator, trust=1.0, learningRate=1e-3,
+                                        learningRateDecay=0.01, weightDecay=0.005, momentum=0.5):
+        """``{module name: LarsSGD}`` for every parameterised leaf module of ``model``;
+        ``lrScheGenerator(module) -> (schedule, is_owner)`` gives each method its schedule and says
+        whether that method reports the learning rate in ``getHyperParameter``."""
+        out = {}
+        for mod in LarsSGD._leaf_modules(model):
+            sched, owner = lrScheGenerator(mod)
+            m = LarsSGD(sched, learningRate, learningRateDecay, weightDecay, momentum, trust)
+            m.lrScheduleOwner = bool(owner)
+            out[mod.get_name()] = m
+        return out
+
+    @staticmethod
+    def createOptimForModule(model, trust=1.0, learningRate=1e-3, learningRateDecay=0.01, weightDecay=0.005,
+                             momentum=0.5, learningRateSchedule=None):
+        """``{module name: LarsSGD}`` whose methods share ONE schedule object; the first method owns
+        it (the only one whose ``getHyperParameter`` prints the rate)."""
+        sched = learningRateSchedule if learningRateSchedule is not None else Default()
+        first = [True]
+
+        def gen(_mod):
+            owner, first[0] = first[0], False
+            return sched, owner
+        return LarsSGD.createOptimLRSchedulerForModule(model, gen, trust, learningRate, learningRateDecay,
+                                                       weightDecay, momentum)
+
+    @staticmethod
+    def containsLarsSGD(optim_methods):
+        """Weight decay of the first ``LarsSGD`` among ``optim_methods`` (a dict), else None."""
+        for m in optim_methods.values():
+            if isinstance(m, LarsSGD):
+                return m.weightDecay
+        return None
 
     def optimize(self, feval, x):
         self.updateHyperParameter()

@@ -281,6 +281,20 @@ class BaseOptimizer:
             for name, meth in self.optim_methods.items():
                 off, n = self._method_slices[name]
                 meth._reg_decay = reg[off:off + n]
+        self._lars_plan = self._make_arena_lars_plan()
+
+    def _make_arena_lars_plan(self):
+        """A :class:`bigdl.optim.lars.LarsPlan` over the whole arena for the LarsSGD methods, when the
+        weights are on the GPU and ``bigdl.lars.fused`` is on; None otherwise (on the CPU the
+        per-method ``LarsSGD.optimize`` loop runs)."""
+        from .lars import LarsPlan, lars_methods
+        lars = lars_methods(self.optim_methods)
+        if (not lars or self.flat is None or not self.flat.weight.is_cuda
+                or not config.get_property("bigdl.lars.fused")):
+            return None
+        # the arena holds whole layers on every rank: the layer sums are complete without a collective
+        return LarsPlan(lars, self._method_slices, lambda lo, hi: [(lo, hi, 0)], self.flat.weight.numel(),
+                        self.flat.weight.device)
 
     def _fold_regularizers(self):
         """Fold every pure-L2 ``wRegularizer``/``bRegularizer`` (``Regularizer.scala``: g += λ·w
@@ -329,8 +343,13 @@ class BaseOptimizer:
             lo = min(offs)
             hi = max(o + n for o, n in zip(offs, lens))
             slices[name] = (lo, hi - lo)
-        covered = sum(l for _, l in slices.values())
-        if covered != self.flat.numel:
+        # every parameter in exactly one method's range; a bucketed arena also holds padding, which
+        # belongs to no parameter (and may sit inside a range whose module spans two buckets)
+        spans = sorted(slices.values())
+        overlap = any(a[0] + a[1] > b[0] for a, b in zip(spans, spans[1:]))
+        covered = sum(n for (_m, _w, _g, o, n, _s) in self.flat.slices
+                      if any(lo <= o and o + n <= lo + ln for lo, ln in spans))
+        if overlap or covered != sum(s[4] for s in self.flat.slices):
             raise ValueError("optimMethods must cover every trainable parameter exactly once")
         return slices
 
@@ -343,8 +362,15 @@ class BaseOptimizer:
         from ..ops import native_ops as NO
         NO.join_wgrad()  # weight gradients computed on the side stream
         self._clip(self.flat.grad, self.flat.grad)
+        plan = getattr(self, "_lars_plan", None)
         with self.tracer.phase("compute weight"):
+            if plan is not None:
+                # every LarsSGD at once: layer norms, then one fused update over the arena
+                plan.begin(self.flat.weight, self.flat.grad)
+                plan.update(self.flat.weight, self.flat.grad, self.flat.shadow, plan.methods[0].grad_scale)
             for name, meth in self.optim_methods.items():
+                if plan is not None and plan.covers(meth):
+                    continue
                 off, n = self._method_slices[name]
                 w = self.flat.weight[off:off + n]
                 g = self.flat.grad[off:off + n]
@@ -724,9 +750,13 @@ class BaseOptimizer:
         the host snapshot and leaves serialisation + file writes to the checkpoint writer thread."""
         from ..serialization.checkpoint import save_checkpoint
         self._flush_weights()
+        if getattr(self, "_lars_plan", None) is not None:
+            self._lars_plan.export_state()
         if Engine.rank() == 0:
             save_checkpoint(self.checkpoint_path, self.model, self.optim_methods, self.state, self.is_overwrite,
                             asynchronous=asynchronous, slices=getattr(self, "_method_slices", None))
+        if getattr(self, "_lars_plan", None) is not None:
+            self._lars_plan.release_state()  # the writer holds its own snapshot
 
     def _maybe_resume(self):
         """Resume from the latest checkpoint when this process is a launcher restart
@@ -792,7 +822,8 @@ class BaseOptimizer:
         self._on_restore()
 
     def _on_restore(self):
-        pass
+        if getattr(self, "_lars_plan", None) is not None:
+            self._lars_plan.import_state()
 
     def _match_restored_methods(self, methods):
         """Pair restored OptimMethods with the live ones: by the arena slice each owns when the

@@ -143,7 +143,9 @@ class DistriOptimizer(BaseOptimizer):
         if self.device.type == "cuda" and self.compute_dtype != torch.float32:
             self.flat.enable_shadow(self.compute_dtype)
         self._method_slices = self._compute_method_slices()
-        if self.sharded and not all(meth.supports_slices for meth in self.optim_methods.values()):
+        # LarsSGD shards through a LarsPlan (layer norms completed by one all-reduce of 2·L floats)
+        if self.sharded and not all(meth.supports_slices or getattr(meth, "supports_layer_shards", False)
+                                    for meth in self.optim_methods.values()):
             log.info("OptimMethod without slice support: using replicated (all-reduce) mode")
             self.sharded = False
         # buckets + shard space
@@ -191,6 +193,7 @@ class DistriOptimizer(BaseOptimizer):
             meth.grad_scale = 1.0 / W
             for k in ("epoch", "neval"):
                 meth.state.setdefault(k, self.state[k])
+        self._lars_plan = self._make_shard_lars_plan(soff) if self.sharded else self._make_arena_lars_plan()
         # per-element vectors (folded L2 regularizers, user lr/decay vectors) in the coordinate
         # space the method's update sees: arena slices (replicated) or this rank's shard (sharded)
         reg_full = self._fold_regularizers()
@@ -243,6 +246,25 @@ class DistriOptimizer(BaseOptimizer):
         self._skipped = False
         log.info(f"DistriOptimizer: world={W} params={self.flat.numel} buckets={len(self.buckets)} "
                  f"mode={'sharded' if self.sharded else 'replicated'} comm={self.comm_dtype} overlap={self.overlap}")
+
+    def _make_shard_lars_plan(self, soff):
+        """The LarsPlan of sharded mode: its space is this rank's shard, its pieces the
+        intersections of each layer with every bucket's owned range (as ``_method_shard_ranges``)."""
+        from ..optim.lars import LarsPlan, lars_methods
+        lars = lars_methods(self.optim_methods)
+        if not lars:
+            return None
+
+        def to_shard(lo, hi):
+            out = []
+            for b in self.buckets:
+                per = b.shi - b.slo
+                own_lo = b.lo + self.rank * per
+                a, z = max(lo, own_lo), min(hi, own_lo + per)
+                if a < z:
+                    out.append((b.slo + (a - own_lo), b.slo + (z - own_lo), b.idx))
+            return out
+        return LarsPlan(lars, self._method_slices, to_shard, soff, self.flat.weight.device, self._global_sum)
 
     def _install_hooks(self):
         seen = set()
@@ -379,8 +401,10 @@ class DistriOptimizer(BaseOptimizer):
                                 and not self._drop_mode())
         # early (in-backward) shard updates: sharded, no clipping (which needs the global gradient
         # norm before any update)
+        # ... and no LarsPlan (its layer norms need every bucket's reduced gradient)
         self._early = (self._overlap_active and self._early_ok
-                       and self.constant_clip is None and self.l2_clip is None)
+                       and self.constant_clip is None and self.l2_clip is None
+                       and getattr(self, "_lars_plan", None) is None)
         if self._drop_mode():
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
@@ -510,9 +534,18 @@ class DistriOptimizer(BaseOptimizer):
             for meth in self.optim_methods.values():
                 meth.grad_scale = 1.0
             self._clip(self.shard_g, self.shard_g)
+        plan = self._lars_plan
+        if plan is not None:
+            # the layer norms read the whole reduced gradient shard; clipping (above) ran first
+            for b in self.buckets:
+                self._finish_reduce(b)
+            self._lars_g = self.shard_g if (self.grad_wire is None or clipping) else self.shard_g_wire
+            self._lars_scale = 1.0 if clipping else 1.0 / fin
+            plan.begin(self.shard_w, self._lars_g)
         if not self._early:
             for meth in self.optim_methods.values():
-                meth.begin_iteration(self.shard_w)
+                if plan is None or not plan.covers(meth):
+                    meth.begin_iteration(self.shard_w)
         else:
             # buckets updated during backward: the compute stream must not touch their gradients /
             # weights (next zeroGrad, forward) before the comm-side stream has consumed them
@@ -542,13 +575,19 @@ class DistriOptimizer(BaseOptimizer):
         return self.shard_g
 
     def _update_bucket(self, b: _Bucket):
+        plan = self._lars_plan
+        write_shadow = self.shard_shadow is not None and (self._alias or self.comm_dtype.startswith("bf16"))
         with self.tracer.phase("compute weight"):
             for name, meth in self.optim_methods.items():
+                if plan is not None and plan.covers(meth):
+                    continue
                 for (bb, lo, hi) in self._method_shard_ranges[name]:
                     if bb is b:
-                        sh = self.shard_shadow[lo:hi] if (self.shard_shadow is not None and (
-                            self._alias or self.comm_dtype.startswith("bf16"))) else None
+                        sh = self.shard_shadow[lo:hi] if write_shadow else None
                         meth.apply_update(self.shard_w, self._grad_for(meth, b), lo, hi, shadow=sh)
+            if plan is not None:
+                plan.update(self.shard_w, self._lars_g, self.shard_shadow if write_shadow else None,
+                            self._lars_scale, group=b.idx)
 
     def _update_order(self):
         """Buckets in the order their shard update + all-gather is issued: readiness order (the
@@ -591,12 +630,16 @@ class DistriOptimizer(BaseOptimizer):
         fp32x3.mark_dirty(self.flat.weight)
         if self.flat.shadow is not None:
             self.flat.refresh_shadow()
+        if self._lars_plan is not None:
+            self._lars_plan.import_state()
 
     def checkpoint(self, asynchronous: bool = False):
         """Gather the shards (X14) then rank 0 writes ``model.<neval>`` / ``optimMethod-*``.
         Optimizer state is per shard: each rank writes its own state file next to it."""
         from ..serialization.checkpoint import save_checkpoint, save_shard_state, wait_checkpoints
         self._flush_weights()
+        if self._lars_plan is not None:
+            self._lars_plan.export_state()
         if Engine.rank() == 0:
             save_checkpoint(self.checkpoint_path, self.model, self.optim_methods, self.state, self.is_overwrite,
                             world_size=self.world, sharded=self.sharded, asynchronous=asynchronous,
@@ -604,6 +647,8 @@ class DistriOptimizer(BaseOptimizer):
         if self.sharded:
             save_shard_state(self.checkpoint_path, self.optim_methods, self.state, self.rank, self.is_overwrite,
                              asynchronous=asynchronous, slices=self._method_slices)
+        if self._lars_plan is not None:
+            self._lars_plan.release_state()  # the writers hold their own snapshots
         if not asynchronous:
             wait_checkpoints()
         comm.barrier()

@@ -90,7 +90,12 @@ class LarsProcessor(ParameterProcessor):
     ``parameter_splits`` maps a layer name to its (offset, length) in the flat arena;
     ``shard_range`` is the (offset, length) of this rank's shard.  The per-layer Σw², Σg² of the
     local intersection are packed into ONE vector and summed across ranks with a single collective
-    (the reference's ``reduceByKey``).  Result: ``state["larsScale"][name]`` (python floats)."""
+    (the reference's ``reduceByKey``).  Result: ``state["larsScale"][name]`` (python floats).
+
+    Reading the scales back as Python floats synchronises the host with the device, so no optimizer
+    installs this processor: the device-side equivalent is :class:`bigdl.optim.lars.LarsPlan`, which
+    keeps the layer sums, the all-reduce and the per-layer rate on the device (``ops.lars_sumsq`` /
+    ``ops.lars_step``) and is what the Local and Distri optimizers run for ``LarsSGD``."""
 
     def __init__(self, parameter_splits: Dict[str, Tuple[int, int]], weight_decay: float,
                  shard_range: Optional[Tuple[int, int]] = None):
