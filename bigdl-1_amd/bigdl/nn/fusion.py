@@ -23,6 +23,11 @@ stay identical); matched modules get execution flags instead:
   epilogue, (dgrad + shortcut gradient) · [block output > 0] and the tail BN's Σg, Σg·(x − mean),
   so the tail BN backward is a single apply pass and the masked gradient IS the shortcut gradient.
 
+* BN → ReLU → 3×3 / stride-2 max-pool (``bnpool``, the ResNet stem): in bf16 training the BN only
+  finalizes its statistics and the pool applies BN + ReLU to its window taps while loading them; in
+  backward the pool hands its gradient back deferred and the BN's reduce / apply passes gather it
+  through the argmax on load.  Neither the BN output nor the dense pool gradient is written or read.
+
 Each fusion removes one full read+write pass over an activation tensor from HBM.
 """
 from __future__ import annotations
@@ -32,6 +37,7 @@ from .containers import Sequential, ConcatTable
 from .layers.activation import Threshold
 from .layers.conv import SpatialConvolution
 from .layers.normalization import BatchNormalization, SpatialBatchNormalization
+from .layers.pooling import SpatialMaxPooling
 from .layers.table_ops import CAddTable
 
 
@@ -106,7 +112,7 @@ def _fuse_lstm_stacks(model):
                     _link_stack(n.element, m.element)
 
 
-def fuse(model, convbn=None, bnrelu=None, convsum=None, bnbwd=None, convrelu=None):
+def fuse(model, convbn=None, bnrelu=None, convsum=None, bnbwd=None, convrelu=None, bnpool=None):
     if not config.get_property("bigdl.fusion"):
         return model
     if getattr(model, "_fused", False):
@@ -117,6 +123,7 @@ def fuse(model, convbn=None, bnrelu=None, convsum=None, bnbwd=None, convrelu=Non
     bnrelu = config.get_property("bigdl.fusion.bnrelu") if bnrelu is None else bnrelu
     convsum = config.get_property("bigdl.fusion.convsum") if convsum is None else convsum
     bnbwd = config.get_property("bigdl.fusion.bnbwd") if bnbwd is None else bnbwd
+    bnpool = config.get_property("bigdl.fusion.bnpool") if bnpool is None else bnpool
     tails, heads = [], []
     for s in model.flattened_modules():
         if not isinstance(s, Sequential):
@@ -139,6 +146,10 @@ def fuse(model, convbn=None, bnrelu=None, convsum=None, bnbwd=None, convrelu=Non
                     c._bn_bwd_target = a
                     if type(c) in _PLAIN_CONVS:
                         a._pro_consumer = c  # fp32: its output may reach c deferred (bigdl.fp32.bnPrologue)
+                if (bnpool and type(c) is SpatialMaxPooling and c._bnpool_ok() and a._pool_consumer is None
+                        and c._bn_producer is None):
+                    a._pool_consumer = c  # bf16: its output may reach c deferred, its gradient comes back so
+                    c._bn_producer = a
         if not convsum:
             continue
         for i in range(len(mods) - 1):
@@ -227,8 +238,12 @@ def unfuse(model):
             m._fused_relu = False
             m._defer_ok = False
             m._pro_consumer = None
+            m._pool_consumer = None
             m._pending_stats = None
             m._pending_grad = None
+        if isinstance(m, SpatialMaxPooling):
+            m._bn_producer = None
+            m._bn_in = None
         if isinstance(m, Threshold):
             m._passthrough = False
         if isinstance(m, ConcatTable):

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from ... import ops
-from ...ops.reference import BNGrad, BNOut, StridedGrad, as_dense
+from ...ops.reference import BNGrad, BNOut, DeferredBN, StridedGrad, as_dense
 from ...utils.engine import Engine
 from ...utils import config
 from ..abstractnn import AbstractModule, TensorModule, AutogradModule
@@ -210,7 +210,7 @@ class SpatialConvolution(TensorModule):
             y = self._pro_forward(pro[0], pro[1])
             if y is not NotImplemented:
                 return y
-        if isinstance(input, BNOut):
+        if isinstance(input, DeferredBN):
             input = input.dense()
         x, pad, batched, _ = self._prep(input)
         w4 = self._w4(self.cw("weight"))
@@ -270,7 +270,7 @@ class SpatialConvolution(TensorModule):
             r = self._pro_backward(pro[0], pro[1], gradOutput, need_input, acc)
             if r is not NotImplemented:
                 return r
-        if isinstance(input, BNOut):
+        if isinstance(input, DeferredBN):
             input = input.dense()
         x, pad, batched, pads = self._prep(input)
         if isinstance(gradOutput, BNGrad):

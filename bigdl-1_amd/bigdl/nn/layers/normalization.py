@@ -149,6 +149,13 @@ class BatchNormalization(TensorModule):
     _pending_grad = None
     #: ReLU mask of the last fused-tail forward output as bits (uint8, one byte per 8 channels)
     _relu_bits = None
+    #: the 3×3 / stride-2 max-pool consuming this BN + ReLU's output (nn/fusion.py, bnpool): in bf16
+    #: training the output is handed over deferred (BNPoolOut) and applied while the pool loads its window
+    #: taps; the pool's input gradient comes back deferred too (PoolGrad) and is gathered on load by
+    #: this BN's backward passes
+    _pool_consumer = None
+    #: whether the last training forward added a residual (its ReLU mask then needs y or the mask bits)
+    _last_res = False
 
     def _atomic_sums(self, kind, C, device):
         """Persistent zeroed fp32 [2C + 1] buffer (Σ, Σ², arrival counter) a conv epilogue ADDS this BN's
@@ -261,6 +268,15 @@ class BatchNormalization(TensorModule):
         from ...ops import fp32x3 as F3
         return F3.pro_ok(x, coef)
 
+    def _pool_deferrable(self, x, relu, residual):
+        """bf16 training on the GPU: hand this BN + ReLU's output to its max-pool consumer deferred
+        (bigdl.fusion.bnpool)."""
+        c = self._pool_consumer
+        return (c is not None and relu and residual is None and x.is_cuda and x.dtype == torch.bfloat16
+                and x.dim() == 4 and x.shape[1] % 8 == 0 and x.is_contiguous(memory_format=torch.channels_last)
+                and c._bn_producer is self and c.train and c._bnpool_ok()
+                and bool(config.get_property("bigdl.fusion.bnpool")) and ops.native_has("maxpool2d_forward"))
+
     def forward_residual(self, x, residual, relu):
         """y = [relu](BN(x) + residual) — the fused ResNet block tail (K9)."""
         self._residual_mode = True
@@ -275,7 +291,7 @@ class BatchNormalization(TensorModule):
         return self._forward_impl(input, None, self._fused_relu)
 
     def _forward_impl(self, input, residual, relu):
-        from ...ops.reference import BNOut
+        from ...ops.reference import BNOut, BNPoolOut
         x = input
         if x.dim() == 1:
             x = x.unsqueeze(0)
@@ -293,6 +309,7 @@ class BatchNormalization(TensorModule):
         b = self.cw("bias", pdt) if self.affine else None
         ib = self._in_bias()
         self._last_relu = relu
+        self._last_res = residual is not None
         if self.train:
             if self._sync_active():
                 y, mean, invstd = self._sync_forward(x, g, b, relu, residual, ib, defer=defer)
@@ -305,16 +322,19 @@ class BatchNormalization(TensorModule):
                 ps, self._pending_stats = self._pending_stats, None
                 bits = self._tail_bits(x, relu, residual)
                 self._relu_bits = None
+                pooldefer = False
                 if ps is not None and ps[0] == x.data_ptr() and ps[1] == tuple(x.shape):
-                    special = defer or deferred_res
+                    # bf16: a BN + ReLU whose consumer max-pool applies it on load (finalize only)
+                    pooldefer = not (defer or deferred_res) and self._pool_deferrable(x, relu, residual)
+                    special = defer or deferred_res or pooldefer
                     # fp32: a mid-block BN + ReLU whose consumer conv applies it on load
                     pdefer = not special and self._pro_deferrable(x, relu, residual, coef)
                     r = ops.native_ops.batchnorm_forward_train_partials(
                         x, ps[2], ps[3], g, b, self.runningMean, self.runningVar, self.momentum, self.eps,
                         relu=relu, residual=residual, in_bias=ib, coef_out=coef, shift=ps[4],
-                        bits_out=None if pdefer else bits,
+                        bits_out=None if (pdefer or pooldefer) else bits,
                         rezero=self._is_rep(ps[2]), zero_next=None if special else self._rep_next("fwd", ps[2]),
-                        mean_out=self._shift_next(ps[4]), apply=not (defer or pdefer))
+                        mean_out=self._shift_next(ps[4]), apply=not (defer or pdefer or pooldefer))
                     if r is not NotImplemented and not special:
                         # (the special path finalizes without the one-launch fold: it cleared the set
                         # it read, the other set may still hold a folded step's sums — stay on this one)
@@ -329,7 +349,7 @@ class BatchNormalization(TensorModule):
                 self._relu_bits = bits
                 y, mean, invstd = r
                 if y is None:  # finalize only: the consumer (fused block tail / conv prologue) applies it
-                    y = BNOut(x, coef, relu=bool(relu))
+                    y = BNPoolOut(x, coef, relu=True) if pooldefer else BNOut(x, coef, relu=bool(relu))
                 self._advance_shift(mean)
                 self._last_input = x
             self.saveMean, self.saveStd = mean, invstd
@@ -449,7 +469,63 @@ class BatchNormalization(TensorModule):
         self._drop_sums(ps, 3)  # replicated statistics left by the conv and not read: clear them
         return r
 
+    def _bwd_pool(self, input, pg, need_input, acc):
+        """Backward from the deferred gradient of the max-pool that consumed this BN + ReLU's deferred
+        output: the pool's input gradient is gathered, and the ReLU mask recomputed from the forward
+        coefficients, inside the BN backward passes.  NotImplemented: the caller densifies ``pg``."""
+        out = self.output
+        if (pg.src is not out or not self.train or self._sync_active() or self.scale_w != self.scale_b
+                or input.dim() != 4 or not getattr(self, "_last_relu", False) or self._last_res):
+            return NotImplemented
+        x = to_device_layout(input)
+        if x is not out.x and x.data_ptr() != out.x.data_ptr():
+            return NotImplemented
+        impl = ops.native_ops if (x.is_cuda and ops.native_has("batchnorm_backward")) else ops.reference
+        if x.is_cuda and impl is ops.reference:
+            return NotImplemented
+        g = self.cw("weight", torch.float64 if x.dtype == torch.float64 else torch.float32) if self.affine else None
+        prod = self._bias_producer
+        cb = prod.gradBias if (acc and prod is not None and getattr(prod, "withBias", False)) else None
+        cbs = prod.scale_b if prod is not None else 0.0
+        self._drop_sums(self._pending_grad, 2)
+        self._pending_grad = None
+        return impl.batchnorm_backward_pool(pg, x, g, self.saveMean, self.saveStd, fcoef=out.coef,
+                                            need_input=need_input,
+                                            gg_acc=self.gradWeight if (acc and self.affine) else None,
+                                            gb_acc=self.gradBias if (acc and self.affine) else None,
+                                            scale=self.scale_w if acc else 0.0, cbias_acc=cb, cbias_scale=cbs)
+
+    def _same_input(self, x):
+        li = self._last_input
+        return li is not None and (li is x or (li.data_ptr() == x.data_ptr() and li.shape == x.shape
+                                               and li.stride() == x.stride()))
+
+    def _mask_source(self, x, y, relu):
+        """What the standalone BN + ReLU backward takes its ReLU mask from: → (y, fcoef, mask_bits).
+        The bf16 kernels recompute it from the forward coefficients (a BN without residual) or read the
+        fused tail's mask bits, 0 or 1/16 of the bytes of y; every other path keeps y."""
+        from ...ops.reference import DeferredBN as BNOut
+        if not (relu and self.train and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.shape[1] % 8 == 0 and self._same_input(x) and ops.native_has("batchnorm_backward")):
+            return (y.dense() if isinstance(y, BNOut) else y), None, None
+        C_ = x.shape[1]
+        if not self._last_res:
+            coef = y.coef if isinstance(y, BNOut) else self._coef
+            if coef is not None and coef.numel() == 2 * C_ and coef.device == x.device:
+                return None, coef, None
+        elif not isinstance(y, BNOut):
+            bits = self._relu_bits
+            if bits is not None and bits.numel() == x.numel() // 8 and bits.device == x.device:
+                return None, None, bits
+        return (y.dense() if isinstance(y, BNOut) else y), None, None
+
     def _bwd(self, input, gradOutput, need_input, acc, want_gres=False):
+        from ...ops.reference import PoolGrad
+        if isinstance(gradOutput, PoolGrad):
+            gi = self._bwd_pool(input, gradOutput, need_input, acc)
+            if gi is not NotImplemented:
+                return (gi, None) if want_gres else gi
+            gradOutput = gradOutput.dense()
         x = input if input.dim() > 1 else input.unsqueeze(0)
         gy = gradOutput if gradOutput.dim() > 1 else gradOutput.unsqueeze(0)
         if x.dim() == 4:
@@ -457,10 +533,13 @@ class BatchNormalization(TensorModule):
             gy = to_device_layout(gy)
         relu = getattr(self, "_last_relu", self._fused_relu)
         y = self.output if relu else None
-        from ...ops.reference import BNOut
+        from ...ops.reference import DeferredBN as BNOut
         if isinstance(y, BNOut):
-            y = None if (self._pending_grad is not None and self._pending_grad[0] == gy.data_ptr()) else y.dense()
-        if y is not None and y.dim() == 1:
+            if self._pending_grad is not None and self._pending_grad[0] == gy.data_ptr():
+                y = None
+            elif self._sync_active() and self.train:
+                y = y.dense()  # (the local path builds it only when the mask cannot be recomputed)
+        if isinstance(y, torch.Tensor) and y.dim() == 1:
             y = y.unsqueeze(0)
         g = self.cw("weight", torch.float64 if x.dtype == torch.float64 else torch.float32) if self.affine else None
         prod = self._bias_producer
@@ -496,14 +575,16 @@ class BatchNormalization(TensorModule):
                         gi = gi.reshape(input.shape)
                     return (gi, gy) if want_gres else gi
             self._drop_sums(pg, 2)  # (reached only when the sums were not consumed)
+            y, fcoef, mbits = self._mask_source(x, y, relu)
+            mkw = {} if (fcoef is None and mbits is None) else dict(fcoef=fcoef, mask_bits=mbits)
             gi, gres = ops.batchnorm_backward(gy, x, g, self.saveMean, self.saveStd, y=y, relu=relu,
-                                              need_input=need_input,
+                                              need_input=need_input, **mkw,
                                               gg_acc=self.gradWeight if (acc and self.affine) else None,
                                               gb_acc=self.gradBias if (acc and self.affine and same) else None,
                                               scale=self.scale_w if acc else 0.0, cbias_acc=cb, cbias_scale=cbs,
                                               want_gres=want_gres)
             if acc and self.affine and not same and self.scale_b != 0:
-                gf = acc_float(gy) * ((y > 0).float() if relu else 1.0)
+                gf = acc_float(gy) * (ops.reference.relu_mask(x, y, fcoef, mbits).float() if relu else 1.0)
                 dims = [d for d in range(gf.dim()) if d != 1]
                 self.gradBias.add_(gf.sum(dims), alpha=self.scale_b)
         if gi is not None and input.dim() == 1:

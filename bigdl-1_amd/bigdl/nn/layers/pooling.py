@@ -82,7 +82,42 @@ class SpatialMaxPooling(TensorModule):
         y = NO.maxpool_i8(input, self.kH, self.kW, self.dH, self.dW, pt, pl, P, Q)
         return None if y is NotImplemented else y
 
+    #: nn/fusion.py bnpool: the BN (+ReLU) producing this pool's input — it may hand its output over
+    #: deferred (ops.reference.BNPoolOut), applied to the window taps while this pool loads them
+    _bn_producer = None
+    #: the deferred BN output the last forward consumed as is (the backward then answers deferred too)
+    _bn_in = None
+
+    def _bnpool_ok(self):
+        """The geometry the fused BN → max-pool kernels cover (3×3, stride 2, pad ≤ 1, floor mode)."""
+        return (self.format == "NCHW" and not self.ceilMode and (self.kW, self.kH, self.dW, self.dH) == (3, 3, 2, 2)
+                and self.padW in (0, 1) and self.padH in (0, 1))
+
+    def _bnpool_forward(self, bnout):
+        """Forward of a deferred BN + ReLU output, or None when this pool cannot take it as is."""
+        if not (self._bnpool_ok() and bnout.dim() == 4 and self.train):
+            return None
+        k, s, p = (self.kH, self.kW), (self.dH, self.dW), (self.padH, self.padW)
+        if bnout.is_cuda:
+            if not ops.native_has("maxpool2d_forward"):
+                return None
+            r = ops.native_ops.bn_maxpool_forward(bnout, k, s, p, False, need_indices=True)
+        else:
+            r = ops.reference.bn_maxpool_forward(bnout, k, s, p, False, need_indices=True)
+        if r is NotImplemented:
+            return None
+        self._indices = r[1]
+        self._bn_in = bnout
+        return r[0]
+
     def updateOutput(self, input):
+        from ...ops.reference import DeferredBN
+        self._bn_in = None
+        if isinstance(input, DeferredBN):
+            y = self._bnpool_forward(input)
+            if y is not None:
+                return y
+            input = input.dense()
         if input.dtype == torch.int8 and getattr(input, "_qscale", None) is not None:
             y = self._int8_forward(input)
             if y is not None:
@@ -97,6 +132,18 @@ class SpatialMaxPooling(TensorModule):
         return self._post(y, batched)
 
     def updateGradInput(self, input, gradOutput):
+        from ...ops.reference import DeferredBN, PoolGrad, as_dense
+        gradOutput = as_dense(gradOutput)
+        if isinstance(input, DeferredBN):
+            if input is self._bn_in and self._indices is not None:
+                # the BN that deferred its output gathers this pool's input gradient in its own backward
+                # passes; any other consumer builds it (PoolGrad.dense)
+                gy = to_device_layout(gradOutput)
+                if gy.dtype != input.dtype:
+                    gy = gy.to(input.dtype)
+                return PoolGrad(gy, self._indices, (self.kH, self.kW), (self.dH, self.dW), (self.padH, self.padW),
+                                input)
+            input = input.dense()
         x, pad, batched, pads = self._prep(input)
         gy = gradOutput
         if self.format == "NHWC":

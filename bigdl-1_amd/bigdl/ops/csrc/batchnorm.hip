@@ -12,7 +12,9 @@
 //
 // Forward (train) = stats (read x) + finalize + apply (read x [+res], write y): 3 passes of HBM
 // traffic — the minimum for a non-fused BN.  Backward = reduce (read gy, x [, y]) + finalize + apply
-// (read gy, x [, y], write gx [, g_res]).
+// (read gy, x [, y], write gx [, g_res]).  The ReLU mask of the backward may instead be recomputed from
+// the forward coefficients or read as bits (y is then not read), and the gradient may be the pooled
+// gradient of a 3×3 / stride-2 max-pool gathered through its argmax on load (BnBwdRow below).
 #include "common.h"
 
 struct BnGeom {
@@ -479,12 +481,122 @@ BIGDL_EXPORT int bigdl_bn_fwd_infer(const void* x, void* y, long long M, int C, 
 }
 
 // ------------------------------------------------------------------------------------------------ backward
-// partial[b][c] = Σ g',  partial[G+b][c] = Σ g'·(x − mean),  g' = gy · [y > 0 if RELU]
-template <bool RELU>
+// Where the two backward passes take the ReLU mask and the upstream gradient from.
+// Mask (template MASK; the first two are the historical RELU = false / true):
+//   kMaskNone  no ReLU;
+//   kMaskY     y > 0, y = the BN + ReLU output (bf16 [M][C]);
+//   kMaskCoef  fma(x, scale, shift) > 0 recomputed from the forward coefficients ([2][C] fp32) — the
+//              same mask (a positive fp32 never rounds to +0 in bf16, see bn_apply_rows), y not read;
+//   kMaskBits  the mask bits a fused block tail's apply wrote, one byte per 8-channel chunk.
+// Gradient (template GATHER): dense gy [M][C], or the 3×3 / stride-2 max-pool gather of pooling.hip's
+// k_maxpool_bwd_k3s2: gy is the POOLED gradient [N][P][Q][C], idx the pool's int8 argmax, and a row
+// (input pixel) sums the ≤ 2 × 2 windows that chose it — in fp32, never rounded to bf16 in between.
+enum { kMaskNone = 0, kMaskY = 1, kMaskCoef = 2, kMaskBits = 3 };
+
+struct BnPoolSrc {
+  const int8_t* idx;
+  int H, W, P, Q, ph, pw;
+};
+
+// The raw loads of one (row, 8-channel group): issue() requests them all, get() unpacks g' (the masked
+// gradient) and x — a caller issues several rows before it uses the first.  The dense streams are read
+// once per pass (non-temporal); the pooled gradient and argmax are shared by neighbouring pixels.
+template <int MASK, bool GATHER>
+struct BnBwdRow {
+  static constexpr int NG = GATHER ? 4 : 1;
+  bigdl_u32x4 g[NG], xq, yq;
+  uint2 a[NG];
+  uint32_t me;   // GATHER: byte k = the window offset that means "window k chose this pixel" (0xFF: no window)
+  uint32_t bits;
+
+  __device__ __forceinline__ void issue(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ x,
+                                        const void* __restrict__ msk, const BnPoolSrc& ps, long long r, int C,
+                                        int cg) {
+    const size_t off = (size_t)r * C + (size_t)cg * 8;
+    xq = __builtin_nontemporal_load(reinterpret_cast<const bigdl_u32x4*>(x + off));
+    if (MASK == kMaskY)
+      yq = __builtin_nontemporal_load(reinterpret_cast<const bigdl_u32x4*>(static_cast<const bf16_t*>(msk) + off));
+    if (MASK == kMaskBits) bits = static_cast<const uint8_t*>(msk)[off >> 3];
+    if (!GATHER) {
+      g[0] = __builtin_nontemporal_load(reinterpret_cast<const bigdl_u32x4*>(gy + off));
+      return;
+    }
+    // (the launcher guarantees M = N·H·W < 2^31)
+    const unsigned ru = (unsigned)r, HW = (unsigned)ps.H * (unsigned)ps.W;
+    const unsigned n = ru / HW, rem = ru - n * HW;
+    const int h = (int)(rem / (unsigned)ps.W), w = (int)(rem - (unsigned)h * (unsigned)ps.W);
+    const int hp = h + ps.ph, wp = w + ps.pw;
+    // windows p with 2p ≤ hp ≤ 2p + 2: p ∈ {hp/2 − 1, hp/2} (clipped to [0, P)); absent ones are
+    // masked and read window (0, 0) of the image, exactly like k_maxpool_bwd_k3s2
+    const int pa = hp / 2 - 1, qa = wp / 2 - 1;
+    me = 0;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int v2 = 0; v2 < 2; ++v2) {
+        const int p = pa + u, q = qa + v2, k = 2 * u + v2;
+        const int i = hp - 2 * p, j = wp - 2 * q;
+        const bool ok = p >= 0 && p < ps.P && q >= 0 && q < ps.Q && i <= 2 && j <= 2;
+        me |= (ok ? (uint32_t)(i * 3 + j) : 0xFFu) << (8 * k);
+        const int pp = ok ? p : 0, qq = ok ? q : 0;
+        const size_t o = (((size_t)n * ps.P + pp) * ps.Q + qq) * C + (size_t)cg * 8;
+        a[k] = *reinterpret_cast<const uint2*>(ps.idx + o);
+        g[k] = *reinterpret_cast<const bigdl_u32x4*>(gy + o);
+      }
+  }
+
+  // fsc / fsh: this thread's 8 forward scale / shift values (kMaskCoef only)
+  __device__ __forceinline__ void get(const float* fsc, const float* fsh, float* gv, float* xv) const {
+    unpack8(make_uint4(xq[0], xq[1], xq[2], xq[3]), xv);
+    if (!GATHER) {
+      unpack8(make_uint4(g[0][0], g[0][1], g[0][2], g[0][3]), gv);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gv[e] = 0.f;
+#pragma unroll
+      for (int k = 0; k < NG; ++k) {
+        float t[8];
+        unpack8(make_uint4(g[k][0], g[k][1], g[k][2], g[k][3]), t);
+        const uint32_t aw[2] = {a[k].x, a[k].y};
+        const uint32_t mk = (me >> (8 * k)) & 0xFFu;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (((aw[e >> 2] >> (8 * (e & 3))) & 0xFFu) == mk) gv[e] += t[e];
+      }
+    }
+    if (MASK == kMaskY) {
+      float yv[8];
+      unpack8(make_uint4(yq[0], yq[1], yq[2], yq[3]), yv);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
+    }
+    if (MASK == kMaskCoef) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gv[k] = fmaf(xv[k], fsc[k], fsh[k]) > 0.f ? gv[k] : 0.f;
+    }
+    if (MASK == kMaskBits) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gv[k] = ((bits >> k) & 1u) ? gv[k] : 0.f;
+    }
+  }
+};
+
+// this thread's forward scale / shift for channel group cg (kMaskCoef: msk = [scale | shift])
+template <int MASK>
+__device__ __forceinline__ void bn_bwd_fcoef(const void* msk, int C, int cg, float* fsc, float* fsh) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    fsc[k] = MASK == kMaskCoef ? static_cast<const float*>(msk)[cg * 8 + k] : 0.f;
+    fsh[k] = MASK == kMaskCoef ? static_cast<const float*>(msk)[C + cg * 8 + k] : 0.f;
+  }
+}
+
+// partial[b][c] = Σ g',  partial[G+b][c] = Σ g'·(x − mean),  g' = the masked (gathered) gradient
+template <int MASK, bool GATHER = false>
 __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ x,
-                                                       const bf16_t* __restrict__ y, long long M, int C,
+                                                       const void* __restrict__ msk, long long M, int C,
                                                        long long rows_per_block, const float* __restrict__ mean,
-                                                       float* __restrict__ partial, int G) {
+                                                       float* __restrict__ partial, int G, BnPoolSrc ps = BnPoolSrc()) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   BnGeom g = bn_geom(C);
   const int t = threadIdx.x;
@@ -495,26 +607,32 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const bf16_t* __restrict_
   if (r1 > M) r1 = M;
   float* s_a = smem;
   float* s_b = smem + g.RPI * C;
+  // rows in flight per thread: the gather form has short rows of work behind many small requests, and
+  // with G ≤ 512 blocks a CU holds only two waves per SIMD, so the registers are there
+  constexpr int U = GATHER ? 4 : 1;
   for (int cg = cg_local; cg < g.CG; cg += g.tpr) {
     if (r_off >= g.RPI) break;
-    float mu[8], a[8], b[8];
+    float mu[8], a[8], b[8], fsc[8], fsh[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) { mu[k] = mean[cg * 8 + k]; a[k] = 0.f; b[k] = 0.f; }
-    for (long long r = r0 + r_off; r < r1; r += g.RPI) {
-      size_t off = (size_t)r * C + (size_t)cg * 8;
-      float gv[8], xv[8];
-      load8_nt(gy + off, gv);
-      load8_nt(x + off, xv);
-      if (RELU) {
-        float yv[8];
-        load8_nt(y + off, yv);
+    bn_bwd_fcoef<MASK>(msk, C, cg, fsc, fsh);
+    for (long long r = r0 + r_off; r < r1; r += (long long)U * g.RPI) {
+      BnBwdRow<MASK, GATHER> row[U];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
+      for (int u = 0; u < U; ++u) {
+        const long long ru = r + (long long)u * g.RPI;
+        row[u].issue(gy, x, msk, ps, ru < r1 ? ru : r, C, cg);
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        a[k] += gv[k];
-        b[k] = fmaf(gv[k], xv[k] - mu[k], b[k]);
+      for (int u = 0; u < U; ++u) {
+        if (r + (long long)u * g.RPI >= r1) break;
+        float gv[8], xv[8];
+        row[u].get(fsc, fsh, gv, xv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          a[k] += gv[k];
+          b[k] = fmaf(gv[k], xv[k] - mu[k], b[k]);
+        }
       }
     }
 #pragma unroll
@@ -570,10 +688,11 @@ __global__ void __launch_bounds__(32 * kFinRG) k_bn_bwd_finalize(const T* __rest
   if (cbias) cbias[c] += cbscale * (A * dbeta + B * Mf * mean[c] + Mf * Cc);
 }
 
-template <bool RELU, bool GRES, int kApplyUnroll>
+template <int MASK, bool GRES, int kApplyUnroll, bool GATHER = false>
 __device__ __forceinline__ void bn_bwd_apply_rows(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ x,
-                                                  const bf16_t* __restrict__ y, bf16_t* __restrict__ gx,
-                                                  bf16_t* __restrict__ gres, long long M, int C, const float* coef) {
+                                                  const void* __restrict__ msk, bf16_t* __restrict__ gx,
+                                                  bf16_t* __restrict__ gres, long long M, int C, const float* coef,
+                                                  const BnPoolSrc& ps = BnPoolSrc()) {
   BnGeom g = bn_geom(C);
   const int t = threadIdx.x;
   const int cg_local = t % g.tpr;
@@ -581,23 +700,21 @@ __device__ __forceinline__ void bn_bwd_apply_rows(const bf16_t* __restrict__ gy,
   if (r_off >= g.RPI) return;
   const long long rstride = (long long)gridDim.x * g.RPI;
   for (int cg = cg_local; cg < g.CG; cg += g.tpr) {
-    float A[8], B[8], Cc[8];
+    float A[8], B[8], Cc[8], fsc[8], fsh[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       A[k] = coef[cg * 8 + k];
       B[k] = coef[C + cg * 8 + k];
       Cc[k] = coef[2 * C + cg * 8 + k];
     }
+    bn_bwd_fcoef<MASK>(msk, C, cg, fsc, fsh);
     long long r = (long long)blockIdx.x * g.RPI + r_off;
     for (; r < M; r += kApplyUnroll * rstride) {  // see k_bn_apply: loads of all rows of a trip first
-      bigdl_u32x4 gq[kApplyUnroll], xq[kApplyUnroll], yq[kApplyUnroll];
+      BnBwdRow<MASK, GATHER> row[kApplyUnroll];
 #pragma unroll
       for (int u = 0; u < kApplyUnroll; ++u) {
         const long long ru = r + u * rstride;
-        const size_t off = (size_t)(ru < M ? ru : r) * C + (size_t)cg * 8;
-        gq[u] = __builtin_nontemporal_load(reinterpret_cast<const bigdl_u32x4*>(gy + off));
-        xq[u] = __builtin_nontemporal_load(reinterpret_cast<const bigdl_u32x4*>(x + off));
-        if (RELU) yq[u] = __builtin_nontemporal_load(reinterpret_cast<const bigdl_u32x4*>(y + off));
+        row[u].issue(gy, x, msk, ps, ru < M ? ru : r, C, cg);
       }
 #pragma unroll
       for (int u = 0; u < kApplyUnroll; ++u) {
@@ -605,14 +722,7 @@ __device__ __forceinline__ void bn_bwd_apply_rows(const bf16_t* __restrict__ gy,
         if (ru >= M) break;
         const size_t off = (size_t)ru * C + (size_t)cg * 8;
         float gv[8], xv[8];
-        unpack8(make_uint4(gq[u][0], gq[u][1], gq[u][2], gq[u][3]), gv);
-        unpack8(make_uint4(xq[u][0], xq[u][1], xq[u][2], xq[u][3]), xv);
-        if (RELU) {
-          float yv[8];
-          unpack8(make_uint4(yq[u][0], yq[u][1], yq[u][2], yq[u][3]), yv);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
-        }
+        row[u].get(fsc, fsh, gv, xv);
         if (GRES) store8(gres + off, gv);
 #pragma unroll
         for (int k = 0; k < 8; ++k) xv[k] = fmaf(A[k], gv[k], fmaf(B[k], xv[k], Cc[k]));
@@ -622,12 +732,12 @@ __device__ __forceinline__ void bn_bwd_apply_rows(const bf16_t* __restrict__ gy,
   }
 }
 
-template <bool RELU, bool GRES, int kApplyUnroll = 4>
+template <int MASK, bool GRES, int kApplyUnroll = 4, bool GATHER = false>
 __global__ void __launch_bounds__(256) k_bn_bwd_apply(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ x,
-                                                      const bf16_t* __restrict__ y, bf16_t* __restrict__ gx,
+                                                      const void* __restrict__ msk, bf16_t* __restrict__ gx,
                                                       bf16_t* __restrict__ gres, long long M, int C,
-                                                      const float* __restrict__ coef) {
-  bn_bwd_apply_rows<RELU, GRES, kApplyUnroll>(gy, x, y, gx, gres, M, C, coef);
+                                                      const float* __restrict__ coef, BnPoolSrc ps = BnPoolSrc()) {
+  bn_bwd_apply_rows<MASK, GRES, kApplyUnroll, GATHER>(gy, x, msk, gx, gres, M, C, coef, ps);
 }
 
 // Backward.  ws: 2·G·C floats; coef: 3·C floats.  gx may be null (no input gradient needed).
@@ -652,11 +762,88 @@ BIGDL_EXPORT int bigdl_bn_bwd(const void* gy, const void* x, const void* y, void
     int grid = apply_grid(M, C);
     const bf16_t *g_ = (const bf16_t*)gy, *x_ = (const bf16_t*)x, *y_ = (const bf16_t*)y;
     bf16_t *gx_ = (bf16_t*)gx, *gr_ = (bf16_t*)gres;
-    if (relu && gres) hipLaunchKernelGGL((k_bn_bwd_apply<true, true>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef);
-    else if (relu) hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<true, false, 1> : k_bn_bwd_apply<true, false, 4>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef);
-    else if (gres) hipLaunchKernelGGL((k_bn_bwd_apply<false, true>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef);
-    else hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<false, false, 1> : k_bn_bwd_apply<false, false, 4>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef);
+    if (relu && gres) hipLaunchKernelGGL((k_bn_bwd_apply<true, true>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef, BnPoolSrc());
+    else if (relu) hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<true, false, 1> : k_bn_bwd_apply<true, false, 4>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef, BnPoolSrc());
+    else if (gres) hipLaunchKernelGGL((k_bn_bwd_apply<false, true>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef, BnPoolSrc());
+    else hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<false, false, 1> : k_bn_bwd_apply<false, false, 4>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, gr_, M, C, coef, BnPoolSrc());
   }
+  BIGDL_CHECK_LAUNCH();
+}
+
+// The passes of bigdl_bn_bwd (reduce, finalize, apply) with the mask / gradient source chosen at
+// compile time; the finalize between them is the same kernel whatever the source.
+template <int MASK, bool GATHER, bool GRES>
+static void launch_bwd_src(const void* gy, const void* x, const void* msk, void* gx, void* gres, long long M, int C,
+                           const float* gamma, const float* mean, const float* invstd, float* ggamma, float* gbeta,
+                           float gscale, float* cbias, float cbscale, float* ws, float* coef, const BnPoolSrc& ps,
+                           hipStream_t s) {
+  const int G = bigdl_bn_num_partials(M, C);
+  const long long rpb = (M + G - 1) / G;
+  hipLaunchKernelGGL((k_bn_bwd_reduce<MASK, GATHER>), dim3(G), dim3(256), stats_smem(C), s, (const bf16_t*)gy,
+                     (const bf16_t*)x, msk, M, C, rpb, mean, ws, G, ps);
+  hipLaunchKernelGGL(k_bn_bwd_finalize<float>, dim3((C + 31) / 32), dim3(32 * kFinRG), 0, s, (const float*)ws, G, M, C,
+                     gamma, mean, invstd, ggamma, gbeta, gscale, cbias, cbscale, coef);
+  if (!gx) return;
+  // the gather form holds 4 gradient + 4 argmax requests per row: 2 rows per trip keep as many
+  // requests in flight as 4 rows of the dense form at half the registers
+  constexpr int U = GATHER ? 2 : 4;
+  hipLaunchKernelGGL((k_bn_bwd_apply<MASK, GRES, U, GATHER>), dim3(apply_grid(M, C)), dim3(256), 0, s,
+                     (const bf16_t*)gy, (const bf16_t*)x, msk, (bf16_t*)gx, (bf16_t*)gres, M, C, coef, ps);
+}
+
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// bigdl_bn_bwd of a BN + ReLU whose mask does not come from y.  mask_kind 2 (kMaskCoef): mask = the
+// BN's forward coefficients [scale | shift] ([2][C] fp32), the mask fma(x, scale, shift) > 0 is
+// recomputed (a BN + ReLU WITHOUT a residual only); 3 (kMaskBits): mask = the ReLU mask bits of the
+// forward apply (uint8 [M·C/8]).  Everything else as bigdl_bn_bwd with relu = 1.
+BIGDL_EXPORT int bigdl_bn_bwd_mask(const void* gy, const void* x, const void* mask, int mask_kind, void* gx, void* gres,
+                                   long long M, int C, const float* gamma, const float* mean, const float* invstd,
+                                   float* ggamma, float* gbeta, float gscale, float* cbias, float cbscale, float* ws,
+                                   float* coef, hipStream_t s) {
+  if (C % 8 || M <= 0 || !gy || !x || !mask || !mean || !invstd || !ws || !coef) return (int)hipErrorInvalidValue;
+  if ((mask_kind != kMaskCoef && mask_kind != kMaskBits) || (gres && !gx)) return (int)hipErrorInvalidValue;
+  if (!al16(gy) || !al16(x) || !al16(gx) || !al16(gres) || stats_smem(C) > 64 * 1024) return (int)hipErrorInvalidValue;
+  const BnPoolSrc ps = BnPoolSrc();
+#define BIGDL_BWD_SRC(MK, GR) \
+  launch_bwd_src<MK, false, GR>(gy, x, mask, gx, gres, M, C, gamma, mean, invstd, ggamma, gbeta, gscale, cbias, \
+                                cbscale, ws, coef, ps, s)
+  if (mask_kind == kMaskCoef) {
+    if (gres) BIGDL_BWD_SRC(kMaskCoef, true);
+    else BIGDL_BWD_SRC(kMaskCoef, false);
+  } else {
+    if (gres) BIGDL_BWD_SRC(kMaskBits, true);
+    else BIGDL_BWD_SRC(kMaskBits, false);
+  }
+#undef BIGDL_BWD_SRC
+  BIGDL_CHECK_LAUNCH();
+}
+
+// Backward of BN [+ ReLU] → 3×3 / stride-2 max-pool in one: gp is the POOLED gradient [N][P][Q][C]
+// (bf16), idx the pool's int8 argmax; both passes gather the pool's input gradient on load (in fp32),
+// so the dense [N][H][W][C] pool gradient is never written or read.  fcoef (nullable): the BN's
+// forward [scale | shift] — given, the ReLU mask fma(x, scale, shift) > 0 is applied; null = no ReLU.
+// The geometry of k_maxpool_bwd_k3s2 only: pad ≤ 1, C % 8 == 0, N·H·W < 2^31.
+BIGDL_EXPORT int bigdl_bn_bwd_pool(const void* gp, const void* idx, const void* x, const float* fcoef, void* gx, int N,
+                                   int H, int W, int C, int P, int Q, int ph, int pw, const float* gamma,
+                                   const float* mean, const float* invstd, float* ggamma, float* gbeta, float gscale,
+                                   float* cbias, float cbscale, float* ws, float* coef, hipStream_t s) {
+  if (C <= 0 || C % 8 || N <= 0 || H <= 0 || W <= 0 || P <= 0 || Q <= 0 || ph < 0 || ph > 1 || pw < 0 || pw > 1)
+    return (int)hipErrorInvalidValue;
+  if (!gp || !idx || !x || !mean || !invstd || !ws || !coef) return (int)hipErrorInvalidValue;
+  const long long M = (long long)N * H * W;
+  if (M >= 0x7fffffffLL || (long long)H * W >= 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  if (!al16(gp) || !al16(x) || !al16(gx) || ((uintptr_t)idx & 7) || stats_smem(C) > 64 * 1024)
+    return (int)hipErrorInvalidValue;
+  BnPoolSrc ps;
+  ps.idx = (const int8_t*)idx;
+  ps.H = H; ps.W = W; ps.P = P; ps.Q = Q; ps.ph = ph; ps.pw = pw;
+  if (fcoef)
+    launch_bwd_src<kMaskCoef, true, false>(gp, x, fcoef, gx, nullptr, M, C, gamma, mean, invstd, ggamma, gbeta, gscale,
+                                           cbias, cbscale, ws, coef, ps, s);
+  else
+    launch_bwd_src<kMaskNone, true, false>(gp, x, nullptr, gx, nullptr, M, C, gamma, mean, invstd, ggamma, gbeta,
+                                           gscale, cbias, cbscale, ws, coef, ps, s);
   BIGDL_CHECK_LAUNCH();
 }
 
@@ -678,7 +865,7 @@ BIGDL_EXPORT int bigdl_bn_bwd_partials(const void* gm, const void* x, void* gx, 
   if (gx) {
     int grid = apply_grid(M, C);
     hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<false, false, 1> : k_bn_bwd_apply<false, false, 4>), dim3(grid), dim3(256), 0, s, (const bf16_t*)gm,
-                       (const bf16_t*)x, (const bf16_t*)nullptr, (bf16_t*)gx, (bf16_t*)nullptr, M, C, coef);
+                       (const bf16_t*)x, (const bf16_t*)nullptr, (bf16_t*)gx, (bf16_t*)nullptr, M, C, coef, BnPoolSrc());
   }
   BIGDL_CHECK_LAUNCH();
 }
@@ -690,7 +877,7 @@ BIGDL_EXPORT int bigdl_bn_bwd_apply_coef(const void* gm, const void* x, void* gx
   if (C % 8 || M <= 0 || !gm || !x || !gx || !coef) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<false, false, 1> : k_bn_bwd_apply<false, false, 4>),
                      dim3(apply_grid(M, C)), dim3(256), 0, s, (const bf16_t*)gm, (const bf16_t*)x,
-                     (const bf16_t*)nullptr, (bf16_t*)gx, (bf16_t*)nullptr, M, C, coef);
+                     (const bf16_t*)nullptr, (bf16_t*)gx, (bf16_t*)nullptr, M, C, coef, BnPoolSrc());
   BIGDL_CHECK_LAUNCH();
 }
 
@@ -1217,10 +1404,10 @@ BIGDL_EXPORT int bigdl_bn_bwd_apply_sums(const void* gy, const void* x, const vo
     bf16_t* gx_ = (bf16_t*)gx;
     if (relu)
       hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<true, false, 1> : k_bn_bwd_apply<true, false, 4>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, (bf16_t*)nullptr, M, C,
-                         coef);
+                         coef, BnPoolSrc());
     else
       hipLaunchKernelGGL((apply_unroll1() ? k_bn_bwd_apply<false, false, 1> : k_bn_bwd_apply<false, false, 4>), dim3(grid), dim3(256), 0, s, g_, x_, y_, gx_, (bf16_t*)nullptr, M,
-                         C, coef);
+                         C, coef, BnPoolSrc());
   }
   BIGDL_CHECK_LAUNCH();
 }

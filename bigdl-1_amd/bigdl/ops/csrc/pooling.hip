@@ -126,6 +126,72 @@ __global__ void __launch_bounds__(256) k_maxpool_fwd_k3s2(const T* __restrict__ 
   }
 }
 
+// k_maxpool_fwd_k3s2 on a training BatchNorm's deferred output: x is the BN INPUT and coef its forward
+// coefficients [scale | shift] ([2][C] fp32, k_bn_finalize).  Each tap is bf16([relu](fma(x, scale,
+// shift))) — the formula and rounding of bn_apply_rows (batchnorm.hip) — and the ROUNDED values are
+// compared in the same tap order with the same strict > / NaN rule, so the pooled tensor and the
+// argmax are bit-identical to BN apply → max-pool while the BN output is never written or read.
+template <typename IT, bool RELU>
+__global__ void __launch_bounds__(256) k_bn_maxpool_fwd_k3s2(const bf16_t* __restrict__ x,
+                                                             const float* __restrict__ coef,
+                                                             bf16_t* __restrict__ y, int8_t* __restrict__ idx,
+                                                             PoolGeom g) {
+  const int CG = g.C >> 3;
+  const IT total = (IT)g.N * g.P * g.Q * CG;
+  for (IT t = blockIdx.x * (IT)blockDim.x + threadIdx.x; t < total; t += (IT)gridDim.x * blockDim.x) {
+    const int cg = (int)(t % CG);
+    IT pix = t / CG;
+    const int q = (int)(pix % g.Q);
+    pix /= g.Q;
+    const int p = (int)(pix % g.P);
+    const int n = (int)(pix / g.P);
+    const int h0 = p * 2 - g.ph, w0 = q * 2 - g.pw;
+    const int hc = min(max(h0 + 1, 0), g.H - 1), wc = min(max(w0 + 1, 0), g.W - 1);
+    uint4 raw[9];
+    bool ok[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int h = h0 + i, w = w0 + j;
+        ok[3 * i + j] = (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
+        const int hh = ok[3 * i + j] ? h : hc, ww = ok[3 * i + j] ? w : wc;
+        raw[3 * i + j] = *reinterpret_cast<const uint4*>(x + (((size_t)n * g.H + hh) * g.W + ww) * g.C + cg * 8);
+      }
+    float sc[8], sh[8];
+    pld8(coef + cg * 8, sc);
+    pld8(coef + g.C + cg * 8, sh);
+    float best[8];
+    int arg[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; arg[e] = 0; }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      float v[8];
+      unpack8(raw[k], v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float o = fmaf(v[e], sc[e], sh[e]);
+        if (RELU) o = fmaxf(o, 0.f);
+        o = bf2f(f2bf(o));  // the value the BN apply pass would have stored
+        if (ok[k] && (o > best[e] || o != o)) {  // NaN propagates like torch
+          best[e] = o;
+          arg[e] = k;
+        }
+      }
+    }
+    const size_t o = (((size_t)n * g.P + p) * g.Q + q) * g.C + cg * 8;
+    store8(y + o, best);
+    if (!idx) continue;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lo |= (uint32_t)(arg[e] & 0xFF) << (8 * e);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) hi |= (uint32_t)(arg[4 + e] & 0xFF) << (8 * e);
+    *reinterpret_cast<uint2*>(idx + o) = make_uint2(lo, hi);
+  }
+}
+
 template <typename IT, typename T = bf16_t>
 __global__ void __launch_bounds__(256) k_maxpool_bwd(const T* __restrict__ gy, const int8_t* __restrict__ idx,
                                                      T* __restrict__ gx, PoolGeom g) {
@@ -391,6 +457,32 @@ BIGDL_EXPORT int bigdl_maxpool_fwd(const void* x, void* y, void* idx, int N, int
   } else {
     hipLaunchKernelGGL(k_maxpool_fwd<long long>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (int8_t*)idx, g);
   }
+  BIGDL_CHECK_LAUNCH();
+}
+
+// Max-pool of a deferred training BN (+ReLU) output: x = the BN input, coef = [scale | shift].  Only
+// the geometry of the k3s2 kernel (3×3, stride 2, pad ≤ 1, C % 8 == 0, 32-bit index range); idx may
+// be null (no argmax).
+BIGDL_EXPORT int bigdl_bn_maxpool_fwd(const void* x, const float* coef, void* y, void* idx, int N, int H, int W, int C,
+                                      int P, int Q, int kh, int kw, int sh, int sw, int ph, int pw, int relu,
+                                      hipStream_t s) {
+  if (!x || !coef || !y || N <= 0 || H <= 0 || W <= 0 || P <= 0 || Q <= 0 || C <= 0 || C % 8)
+    return (int)hipErrorInvalidValue;
+  if (kh != 3 || kw != 3 || sh != 2 || sw != 2 || ph < 0 || pw < 0 || ph > 1 || pw > 1) return (int)hipErrorInvalidValue;
+  // every window must start inside the image (P, Q no larger than the floor-mode output size)
+  if (2 * (P - 1) - ph >= H || 2 * (Q - 1) - pw >= W) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)coef & 15) || ((uintptr_t)idx & 7))
+    return (int)hipErrorInvalidValue;
+  const long long total = (long long)N * P * Q * (C / 8);
+  if (total >= 0x7fffffffLL || (long long)N * H * W * (C / 8) >= 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  PoolGeom g = make_geom(N, H, W, C, P, Q, kh, kw, sh, sw, ph, pw);
+  const int grid = bigdl_grid(total, 256, 16384);
+  if (relu)
+    hipLaunchKernelGGL((k_bn_maxpool_fwd_k3s2<uint32_t, true>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, coef,
+                       (bf16_t*)y, (int8_t*)idx, g);
+  else
+    hipLaunchKernelGGL((k_bn_maxpool_fwd_k3s2<uint32_t, false>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, coef,
+                       (bf16_t*)y, (int8_t*)idx, g);
   BIGDL_CHECK_LAUNCH();
 }
 

@@ -540,13 +540,40 @@ def batchnorm_forward_infer(x, gamma, beta, running_mean, running_var, eps, relu
 
 @register("batchnorm_backward")
 def batchnorm_backward(gy, x, gamma, save_mean, save_invstd, y=None, relu=False, need_input=True, gg_acc=None,
-                       gb_acc=None, scale=1.0, cbias_acc=None, cbias_scale=1.0, want_gres=False):
+                       gb_acc=None, scale=1.0, cbias_acc=None, cbias_scale=1.0, want_gres=False, fcoef=None,
+                       mask_bits=None):
     """Returns (gradInput or None, g' or None).  g' is the masked upstream gradient for a fused
-    residual branch (``want_gres``); ``cbias_acc`` receives the gradient of a folded producer bias."""
+    residual branch (``want_gres``); ``cbias_acc`` receives the gradient of a folded producer bias.
+    The ReLU mask comes from ``y``, or without it (bf16) from ``fcoef`` — the forward [scale | shift],
+    recomputed as fma(x, scale, shift) > 0, a BN + ReLU without residual — or from ``mask_bits``, the
+    bits a fused block tail's forward wrote: y is then not read."""
     rc = _rows_c(x)
     if rc is None:
         return NotImplemented
     M, C_ = rc
+    if relu and y is None and (fcoef is not None or mask_bits is not None):
+        if fcoef is not None:
+            kind, msk = 2, fcoef
+            ok = _f32vec(fcoef, 2 * C_)
+        else:
+            kind, msk = 3, mask_bits
+            ok = _bits_ok(mask_bits, M, C_, True) is not None
+        if not (ok and _bn_ok(x, C_) and gy.dtype == _bf16 and gy.shape == x.shape and gy.stride() == x.stride()
+                and _al16(gy) and all(_f32vec(t, C_) for t in (gamma, save_mean, save_invstd, gg_acc, gb_acc,
+                                                               cbias_acc))):
+            return NotImplemented
+        lib = _lib()
+        G = lib.bigdl_bn_num_partials(_ll(M), C.c_int(C_))
+        ws = torch.empty(2 * G * C_, dtype=_f32, device=x.device)
+        coef = torch.empty(3 * C_, dtype=_f32, device=x.device)
+        gx = torch.empty_like(x) if need_input else None
+        gres = torch.empty_like(x) if (want_gres and need_input) else None
+        check(lib.bigdl_bn_bwd_mask(ptr(gy), ptr(x), ptr(msk), C.c_int(kind), ptr(gx), ptr(gres), _ll(M), C.c_int(C_),
+                                    ptr(gamma), ptr(save_mean), ptr(save_invstd), ptr(gg_acc), ptr(gb_acc), _f(scale),
+                                    ptr(cbias_acc), _f(cbias_scale), ptr(ws), ptr(coef), _s()), "bn_bwd_mask")
+        if want_gres and gres is None:
+            gres = gy * R_.relu_mask(x, None, fcoef, mask_bits).to(gy.dtype)
+        return gx, gres
     mb = F3.producer_bits(y) if relu else None  # the forward's ReLU mask bits (1 bit instead of 4 B)
     if (_bn32_ok(x, C_, gy, y if relu and mb is None else None) and (y is not None or not relu)
             and all(_f32vec(t, C_) for t in (gamma, save_mean, save_invstd, gg_acc, gb_acc, cbias_acc))):
@@ -2242,6 +2269,68 @@ def maxpool2d_forward(x, k, s, p, ceil_mode, need_indices=True):
     check(_lib().bigdl_maxpool_fwd(ptr(x), ptr(y), ptr(idx), N_, H, W, C_, P, Q, k[0], k[1], s[0], s[1], p[0], p[1],
                                    _s()), "maxpool_fwd")
     return y, (_Int8Idx(idx) if need_indices else None)
+
+
+def bn_maxpool_forward(bnout, k, s, p, ceil_mode=False, need_indices=True):
+    """Max-pool of a deferred training BN (+ReLU) output (:class:`~bigdl.ops.reference.BNPoolOut`,
+    bigdl.fusion.bnpool): the BN is applied to each window tap on load, rounded to bf16 exactly as the
+    apply pass would have stored it, so the pooled tensor and the argmax are bit-identical to
+    BN apply → max-pool while the BN output is never written.  The 3×3 / stride-2 / pad ≤ 1 floor-mode
+    bf16 geometry only; NotImplemented otherwise (the caller pools ``bnout.dense()``)."""
+    x, coef = bnout.x, bnout.coef
+    if (x.dim() != 4 or x.dtype != _bf16 or not x.is_cuda or not x.is_contiguous(memory_format=torch.channels_last)
+            or not _al16(x) or ceil_mode or tuple(k) != (3, 3) or tuple(s) != (2, 2) or p[0] not in (0, 1)
+            or p[1] not in (0, 1)):
+        return NotImplemented
+    N_, C_, H, W = x.shape
+    if C_ % 8 or not _f32vec(coef, 2 * C_) or not _al16(coef):
+        return NotImplemented
+    P = _pool_out(H, 3, 2, p[0], False)
+    Q = _pool_out(W, 3, 2, p[1], False)
+    if P <= 0 or Q <= 0 or N_ * H * W * (C_ // 8) >= 2 ** 31 - 1:
+        return NotImplemented
+    y = torch.empty((N_, C_, P, Q), dtype=_bf16, device=x.device, memory_format=torch.channels_last)
+    idx = torch.empty((N_, P, Q, C_), dtype=torch.int8, device=x.device) if need_indices else None
+    check(_lib().bigdl_bn_maxpool_fwd(ptr(x), ptr(coef), ptr(y), ptr(idx), N_, H, W, C_, P, Q, 3, 3, 2, 2, p[0], p[1],
+                                      1 if bnout.relu else 0, _s()), "bn_maxpool_fwd")
+    return y, (_Int8Idx(idx) if need_indices else None)
+
+
+def batchnorm_backward_pool(pg, x, gamma, save_mean, save_invstd, fcoef=None, need_input=True, gg_acc=None,
+                            gb_acc=None, scale=1.0, cbias_acc=None, cbias_scale=1.0):
+    """BN [+ ReLU] backward straight from a deferred max-pool gradient (:class:`~bigdl.ops.reference.
+    PoolGrad`): the reduce and apply passes gather the pool's input gradient from the pooled gradient
+    and the int8 argmax while loading (summed in fp32), and recompute the ReLU mask from ``fcoef`` (the
+    forward [scale | shift]; None = no ReLU) — neither the BN output nor the dense pool gradient is
+    read or written.  Returns gradInput (or None) / NotImplemented."""
+    rc = _rows_c(x)
+    if rc is None or x.dim() != 4 or not isinstance(pg.idx, _Int8Idx):
+        return NotImplemented
+    M, C_ = rc
+    N_, _, H, W = x.shape
+    g, idx = pg.g, pg.idx.t
+    if (not _bn_ok(x, C_) or tuple(pg.k) != (3, 3) or tuple(pg.s) != (2, 2) or pg.p[0] not in (0, 1)
+            or pg.p[1] not in (0, 1) or M >= 2 ** 31 - 1 or g.dim() != 4 or g.dtype != _bf16 or not g.is_cuda
+            or not g.is_contiguous(memory_format=torch.channels_last) or not _al16(g)):
+        return NotImplemented
+    P, Q = g.shape[2], g.shape[3]
+    if (tuple(g.shape) != (N_, C_, P, Q) or tuple(idx.shape) != (N_, P, Q, C_) or idx.dtype != torch.int8
+            or not idx.is_contiguous() or idx.data_ptr() % 8 or P != _pool_out(H, 3, 2, pg.p[0], False)
+            or Q != _pool_out(W, 3, 2, pg.p[1], False)):
+        return NotImplemented
+    if fcoef is not None and not _f32vec(fcoef, 2 * C_):
+        return NotImplemented
+    if not all(_f32vec(t, C_) for t in (gamma, save_mean, save_invstd, gg_acc, gb_acc, cbias_acc)):
+        return NotImplemented
+    lib = _lib()
+    G = lib.bigdl_bn_num_partials(_ll(M), C.c_int(C_))
+    ws = torch.empty(2 * G * C_, dtype=_f32, device=x.device)
+    coef = torch.empty(3 * C_, dtype=_f32, device=x.device)
+    gx = torch.empty_like(x) if need_input else None
+    check(lib.bigdl_bn_bwd_pool(ptr(g), ptr(idx), ptr(x), ptr(fcoef), ptr(gx), N_, H, W, C_, P, Q, pg.p[0], pg.p[1],
+                                ptr(gamma), ptr(save_mean), ptr(save_invstd), ptr(gg_acc), ptr(gb_acc), _f(scale),
+                                ptr(cbias_acc), _f(cbias_scale), ptr(ws), ptr(coef), _s()), "bn_bwd_pool")
+    return gx
 
 
 @register("maxpool2d_backward")

@@ -99,7 +99,7 @@ class StridedGrad:
         return out
 
 
-class BNOut:
+class DeferredBN:
     """Deferred output of a training BatchNorm: y = [relu](x·coef[c] + coef[C + c]), with ``x`` the
     BN input and ``coef`` fp32 [scale; shift].  The fused ResNet block tail takes a shortcut BN's
     output this way (no ReLU) and applies it inside its own pass (ops/csrc/batchnorm.hip rcoef); in
@@ -137,6 +137,19 @@ class BNOut:
             else y.to(self.x.dtype)
 
 
+class BNOut(DeferredBN):
+    """The deferred BN output a fused block tail (no ReLU) or an fp32 conv prologue (``relu``) consumes."""
+    __slots__ = ()
+
+
+class BNPoolOut(DeferredBN):
+    """The deferred BN + ReLU output handed to a 3×3 / stride-2 max-pool (bigdl.fusion.bnpool), which
+    applies it to its window taps on load (ops/csrc/pooling.hip k_bn_maxpool_fwd_k3s2) and answers in
+    backward with a :class:`PoolGrad`.  A type of its own: only the pool takes it as is, every other
+    reader — a conv included, whose fp32 prologue path is :class:`BNOut`'s — builds it with :meth:`dense`."""
+    __slots__ = ()
+
+
 class BNGrad:
     """Deferred input gradient of a training BatchNorm: gx = A·g + B·x + Cc per channel, with ``g``
     the (ReLU-masked) gradient at the BN output, ``x`` the BN input and ``coef`` = fp32 [A; B; Cc]
@@ -171,8 +184,41 @@ class BNGrad:
         return (a * self.g.float() + b * self.x.float() + c).to(self.g.dtype)
 
 
+class PoolGrad:
+    """Deferred input gradient of a max-pool whose input was a deferred BN + ReLU output
+    (bigdl.fusion.bnpool): ``g`` is the gradient at the pool OUTPUT, ``idx`` the forward's argmax and
+    ``k``/``s``/``p`` the window geometry; ``src`` is the :class:`DeferredBN` the pool consumed.  The BN
+    that produced ``src`` gathers the pool's input gradient while loading it in its own backward
+    passes (ops/csrc/batchnorm.hip GATHER), so the dense gradient is never written; :meth:`dense`
+    builds it for any other consumer."""
+    __slots__ = ("g", "idx", "k", "s", "p", "src", "shape")
+
+    def __init__(self, g, idx, k, s, p, src):
+        self.g, self.idx, self.k, self.s, self.p, self.src = g, idx, tuple(k), tuple(s), tuple(p), src
+        self.shape = tuple(src.shape)
+
+    @property
+    def dtype(self):
+        return self.g.dtype
+
+    @property
+    def is_cuda(self):
+        return self.g.is_cuda
+
+    def dim(self):
+        return len(self.shape)
+
+    def dense(self):
+        from . import dispatch, native as N
+        # the pool backward reads only the shape / dtype / device of its input argument — unless the
+        # reference op has to recompute a native int8 argmax from the pooled tensor itself
+        direct = isinstance(self.idx, torch.Tensor) or (self.g.is_cuda and N.has("maxpool2d_backward"))
+        return dispatch.maxpool2d_backward(self.g, self.src.x if direct else self.src.dense(), self.idx, self.k,
+                                           self.s, self.p, False)
+
+
 def as_dense(g):
-    return g.dense() if isinstance(g, (StridedGrad, BNGrad)) else g
+    return g.dense() if isinstance(g, (StridedGrad, BNGrad, PoolGrad)) else g
 
 
 def conv_transpose2d_forward(x, w4, b, stride, pad, adj, dilation=(1, 1), groups=1):
@@ -260,17 +306,32 @@ def batchnorm_forward_infer(x, gamma, beta, running_mean, running_var, eps, relu
     return y.to(x.dtype)
 
 
+def relu_mask(x, y=None, fcoef=None, mask_bits=None):
+    """The ReLU mask of a BN + ReLU output from one of its three sources: ``y`` (the output itself),
+    ``fcoef`` (the forward [scale | shift]: fma(x, scale, shift) > 0, a BN without residual) or
+    ``mask_bits`` (NHWC chunk order: byte (pixel·C + c) / 8, bit c % 8)."""
+    if y is not None:
+        return y > 0
+    C = x.shape[1]
+    if fcoef is not None:
+        return DeferredBN(x, fcoef, relu=False).dense() > 0
+    w = (2 ** torch.arange(8, device=x.device, dtype=torch.int32)).view(1, 8)
+    pos = (mask_bits.view(-1, 1).to(torch.int32) & w) != 0
+    return pos.view(x.shape[0], *x.shape[2:], C).permute(0, 3, 1, 2)
+
+
 def batchnorm_backward(gy, x, gamma, save_mean, save_invstd, y=None, relu=False, need_input=True, gg_acc=None,
-                       gb_acc=None, scale=1.0, cbias_acc=None, cbias_scale=1.0, want_gres=False):
+                       gb_acc=None, scale=1.0, cbias_acc=None, cbias_scale=1.0, want_gres=False, fcoef=None,
+                       mask_bits=None):
     """Returns (gradInput, gradGamma, gradBeta) — ``updateGradInputNCHWTrainFloat`` (:1048) and
     ``accGradientNCHWFloat`` (:1970).  With ``relu`` the ReLU mask is taken from ``y`` (the BN+ReLU
-    output) and fused in (K7/K8)."""
+    output), or without it from ``fcoef`` / ``mask_bits`` (:func:`relu_mask`), and fused in (K7/K8)."""
     C = x.shape[1]
     dims = [d for d in range(x.dim()) if d != 1]
     shape = [1, C] + [1] * (x.dim() - 2)
     g = acc_float(gy)
     if relu:
-        g = g * (y > 0).float()
+        g = g * relu_mask(x, y, fcoef, mask_bits).to(g.dtype)
     xhat = (acc_float(x) - save_mean.view(shape)) * save_invstd.view(shape)
     dbeta = g.sum(dim=dims)
     dgamma = (g * xhat).sum(dim=dims)
@@ -408,6 +469,22 @@ def maxpool2d_backward(gy, x, idx, k, s, p, ceil_mode):
     if hasattr(idx, "t") and not isinstance(idx, torch.Tensor):  # native int8 argmax → recompute
         _, idx = maxpool2d_forward(x, k, s, p, ceil_mode)
     return aten.max_pool2d_with_indices_backward(gy, x, list(k), list(s), list(p), [1, 1], ceil_mode, idx)
+
+
+def bn_maxpool_forward(bnout, k, s, p, ceil_mode=False, need_indices=True):
+    """Max-pool of a deferred BN (+ReLU) output (bigdl.fusion.bnpool): the BN apply and the pool, composed."""
+    return maxpool2d_forward(bnout.dense(), k, s, p, ceil_mode, need_indices)
+
+
+def batchnorm_backward_pool(pg, x, gamma, save_mean, save_invstd, fcoef=None, need_input=True, gg_acc=None,
+                            gb_acc=None, scale=1.0, cbias_acc=None, cbias_scale=1.0):
+    """BN [+ ReLU] backward from a deferred max-pool gradient (:class:`PoolGrad`): the pool backward and
+    :func:`batchnorm_backward`, composed; ``fcoef`` (the forward [scale | shift]) given = ReLU fused.
+    Returns gradInput (or None)."""
+    gy = pg.dense()
+    return batchnorm_backward(gy, x, gamma, save_mean, save_invstd, relu=fcoef is not None, need_input=need_input,
+                              gg_acc=gg_acc, gb_acc=gb_acc, scale=scale, cbias_acc=cbias_acc,
+                              cbias_scale=cbias_scale, fcoef=fcoef)[0]
 
 
 def avgpool2d_forward(x, k, s, p, ceil_mode, count_include_pad, divisor=None):

@@ -95,6 +95,7 @@ _REGISTRY = {
     "bigdl.fusion.convstats": (bool, True, "conv epilogue emits the following training BN's statistics"),
     "bigdl.fusion.shortcutbn": (bool, True, "a ResNet block's conv->BN shortcut hands its BN output to the fused tail deferred (input + coefficients), applied inside the tail's pass"),
     "bigdl.fusion.bnbwd": (bool, True, "dgrad epilogue applies the producing BN's ReLU mask and its backward reductions"),
+    "bigdl.fusion.bnpool": (bool, True, "a training BN + ReLU whose only consumer is a 3x3 stride-2 max-pool (the ResNet stem) hands its output over deferred (bf16 on a GPU): the pool applies BN + ReLU to its window taps on load and the BN backward gathers the pool gradient through the argmax on load - the BN output and the dense pool gradient are never written"),
     "bigdl.fusion.bnprologue": (int, 0, "a BN whose producer is a 1x1 stride-1 conv hands it the input gradient "
                                          "deferred (A*g + B*x + C applied in the conv's dgrad / wgrad operand loads): "
                                          "0 off, 1 when the BN is narrower than the conv input, 2 always "
