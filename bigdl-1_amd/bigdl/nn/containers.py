@@ -180,19 +180,95 @@ def _final_conv(m):
     return m if isinstance(m, SpatialConvolution) and not m._fused_relu else None
 
 
-class ConcatPlan:
-    """Zero-copy channel concat for inference (K19): once the output shape of a concat is known for
-    an input shape, the next forward preallocates the NHWC output and every branch's final conv
-    writes its channel slice in its epilogue — the concat copy disappears.  Eval mode on the device
-    only (training keeps separate branch tensors for the backward slices)."""
+def _mask_relu(m):
+    """The mask-``Threshold`` that ends ``m`` (a Sequential ending conv → fused ReLU), else None: the
+    gradient of that branch is the join's gradient slice masked by the join's own output."""
+    from .layers.conv import SpatialConvolution
+    from .layers.activation import Threshold
+    while isinstance(m, Sequential) and m.modules:
+        last = m.modules[-1]
+        if isinstance(last, Threshold):
+            if last._passthrough == "mask" and len(m.modules) > 1:
+                prev = m.modules[-2]
+                if isinstance(prev, SpatialConvolution) and prev._fused_relu:
+                    return last
+            return None
+        m = last
+    return None
 
-    def __init__(self, convs):
+
+def _concat_train():
+    from ..utils import config
+    return bool(config.get_property("bigdl.concat.train"))
+
+
+def _native_join(ts):
+    """Device tensors joined along dim 1 by the one-launch concat kernel, or None (the caller's torch
+    path runs)."""
+    from .. import ops
+    if not (ts and all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts) and ops.native_has("concat_forward")):
+        return None
+    r = ops.native_ops.concat_forward(ts[0], ts[1:])
+    if r is NotImplemented:
+        ops.native.note_fallback("concat_forward", "unsupported", ts)
+        return None
+    return r
+
+
+def _native_split(gy, y, sizes, masks):
+    """Dense gradient parts of a dim-1 join on the device (split + the masked parts' ReLU backward in
+    one launch), or None."""
+    from .. import ops
+    if not (isinstance(gy, torch.Tensor) and gy.is_cuda and ops.native_has("concat_split_backward")):
+        return None
+    r = ops.native_ops.concat_split_backward(gy, y, sizes, masks)
+    if r is NotImplemented:
+        ops.native.note_fallback("concat_split_backward", "unsupported", (gy,))
+        return None
+    return r
+
+
+def _sum_acts(gs):
+    """Sum gradient activities in order: 3 or more same-shape device tensors in one launch
+    (``ops.sum_n``, the bits of the chained adds), anything else through :func:`_add_act`."""
+    if (len(gs) >= 3 and all(isinstance(g, torch.Tensor) and g.is_cuda and g.shape == gs[0].shape
+                             and g.dtype == gs[0].dtype and g.numel() for g in gs) and _concat_train()):
+        from .. import ops
+        if ops.native_has("sum_n"):
+            out, rest = gs[0], gs[1:]
+            while rest and out is not NotImplemented:  # 8 operands per launch: the running sum + 7
+                out, rest = ops.native_ops.sum_n(out, rest[:7]), rest[7:]
+            if out is not NotImplemented:
+                return out
+            ops.native.note_fallback("sum_n", "unsupported", gs)
+    gi = None
+    for g in gs:
+        gi = _add_act(gi, g)
+    return gi
+
+
+class ConcatPlan:
+    """Zero-copy channel concat (K19): once the output shape of a concat is known for an input shape,
+    the next forward preallocates the NHWC output and every branch's final conv writes its channel
+    slice in its epilogue — the concat copy disappears.  On the device only: in eval mode, and in
+    training (``bigdl.concat.train``) for a bf16 input — the backward then takes the branches'
+    gradient slices, and their ReLU masks (``masks``: each branch's mask-``Threshold`` or None), from
+    the shared output (``ops.concat_split_backward``)."""
+
+    def __init__(self, convs, masks=None):
         self.convs = convs
+        self.masks = masks if masks is not None else [None] * len(convs)
         self.shapes = {}
 
-    def arm(self, key, x):
+    def arm(self, key, x, train=False, bf16=None):
+        """``bf16`` (training): the branches run in bf16 (default: ``x`` is bf16)."""
         shp = self.shapes.get(key)
         if shp is None or not (isinstance(x, torch.Tensor) and x.is_cuda) or any(c is None for c in self.convs):
+            return None
+        if bf16 is None:
+            bf16 = x.dtype == torch.bfloat16
+        if train and not (bf16 and _concat_train()
+                          and all(c.nOutputPlane % 8 == 0 for c in self.convs)):
             return None
         big = torch.empty(shp, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
         c0 = 0
@@ -227,11 +303,13 @@ class Concat(Container):
 
     def updateOutput(self, input):
         plan = None
-        if not self.train and self.dimension == 2 and isinstance(input, torch.Tensor) and input.dim() == 4:
+        native = self.train and _concat_train()  # (training with the property off: the torch path)
+        if ((not self.train or native) and self.dimension == 2 and isinstance(input, torch.Tensor)
+                and input.dim() == 4):
             if self._plan is None:
                 self._plan = ConcatPlan([_final_conv(m) for m in self.modules])
             plan = self._plan
-        big = plan.arm(_plan_key(input), input) if plan is not None else None
+        big = plan.arm(_plan_key(input), input, self.train) if plan is not None else None
         try:
             outs = [m.forward(input) for m in self.modules]
         finally:
@@ -242,6 +320,11 @@ class Concat(Container):
             from .layers.table_ops import _tiles_channels
             if _tiles_channels(big, outs):
                 return big
+        out = _native_join(outs) if native and self.dimension == 2 else None
+        if out is not None:
+            if plan is not None:
+                plan.record(_plan_key(input), out)
+            return out
         out = torch.cat(outs, dim=self.dimension - 1)
         if plan is not None:
             if out.is_cuda:
@@ -249,23 +332,52 @@ class Concat(Container):
             plan.record(_plan_key(input), out)
         return out
 
-    def _split_grad(self, gradOutput):
-        return torch.split(gradOutput, self._sizes, dim=self.dimension - 1)
+    def _split_grad(self, gradOutput, flag=False):
+        """The branches' gradients.  On the device, in training, one launch splits ``gradOutput`` and
+        applies the ReLU mask of every branch that ends conv → mask-``Threshold`` (read from this
+        join's own output); with ``flag`` those Thresholds are told, once, to pass their gradient
+        through.  Returns (parts, flagged Thresholds)."""
+        if self.train and self.dimension == 2 and _concat_train() and isinstance(gradOutput, torch.Tensor) \
+                and gradOutput.is_cuda:
+            y = self.output
+            ok = isinstance(y, torch.Tensor) and y.shape == gradOutput.shape and y.dtype == gradOutput.dtype
+            ths = [_mask_relu(m) if ok else None for m in self.modules]
+            parts = _native_split(gradOutput, y if ok else None, self._sizes, [t is not None for t in ths])
+            if parts is not None:
+                ths = [t for t in ths if t is not None]
+                if flag:
+                    for t in ths:
+                        t._premasked = True
+                return parts, ths
+        return [g.contiguous() for g in torch.split(gradOutput, self._sizes, dim=self.dimension - 1)], []
+
+    @staticmethod
+    def _unflag(ths):
+        for t in ths:
+            t.__dict__.pop("_premasked", None)
 
     def updateGradInput(self, input, gradOutput):
-        gi = None
-        for m, g in zip(self.modules, self._split_grad(gradOutput)):
-            gi = _add_act(gi, m.updateGradInput(input, g.contiguous()))
-        return gi
+        parts, ths = self._split_grad(gradOutput, flag=True)
+        try:
+            gis = [m.updateGradInput(input, g) for m, g in zip(self.modules, parts)]
+        finally:
+            self._unflag(ths)
+        return _sum_acts(gis)
 
     def accGradParameters(self, input, gradOutput):
-        for m, g in zip(self.modules, self._split_grad(gradOutput)):
-            m.accGradParameters(input, g.contiguous())
+        # (a branch's mask-Threshold hands its conv the gradInput it cached in updateGradInput, so no
+        # Threshold consumes a flag here and none is set)
+        parts, _ = self._split_grad(gradOutput)
+        for m, g in zip(self.modules, parts):
+            m.accGradParameters(input, g)
 
     def backward(self, input, gradOutput):
-        gi = None
-        for m, g in zip(self.modules, self._split_grad(gradOutput)):
-            gi = _add_act(gi, m.backward(input, g.contiguous()))
+        parts, ths = self._split_grad(gradOutput, flag=True)
+        try:
+            gis = [m.backward(input, g) for m, g in zip(self.modules, parts)]
+        finally:
+            self._unflag(ths)
+        gi = _sum_acts(gis)
         self.gradInput = gi
         return gi
 

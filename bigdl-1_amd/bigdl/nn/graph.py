@@ -15,7 +15,8 @@ import torch
 
 from ..utils.table import Table
 from .abstractnn import AbstractModule
-from .containers import Container, _add_act
+from ..utils.engine import Engine
+from .containers import Container, _add_act, _concat_train, _sum_acts
 from .layers.shape import Identity
 
 
@@ -138,7 +139,9 @@ class Graph(Container):
 
     def _concat_plans(self):
         """JoinTable nodes whose every input is produced by a single-consumer conv (optionally
-        through its fused ReLU) → :class:`ConcatPlan` (zero-copy concat at inference)."""
+        through its fused ReLU) → :class:`ConcatPlan` (zero-copy concat at inference and in bf16
+        training).  The plan also carries, per input, the single-consumer mask-ReLU that produced it:
+        a join with any of those gets a plan that never arms, for the training backward's masks."""
         from .containers import ConcatPlan
         from .layers.activation import Threshold
         from .layers.conv import SpatialConvolution
@@ -147,20 +150,28 @@ class Graph(Container):
         for n in self.forward_order:
             if not isinstance(n.element, JoinTable) or len(n.prev_nodes) < 2:
                 continue
-            convs = []
+            convs, masks = [], []
             for p in n.prev_nodes:
-                c = None
+                c = th = None
                 e = p.element
                 if (isinstance(e, Threshold) and e._passthrough == "mask" and len(p.prev_nodes) == 1
                         and len(p.next_nodes) == 1):
                     q = p.prev_nodes[0]
-                    if isinstance(q.element, SpatialConvolution) and q.element._fused_relu and len(q.next_nodes) == 1:
-                        c = q.element
+                    if isinstance(q.element, SpatialConvolution) and q.element._fused_relu:
+                        th = e  # its gradient is this join's slice: the join's backward can mask it
+                        if len(q.next_nodes) == 1:
+                            c = q.element
                 elif isinstance(e, SpatialConvolution) and not e._fused_relu and len(p.next_nodes) == 1:
                     c = e
                 convs.append(c)
-            if all(c is not None for c in convs) and len({id(c) for c in convs}) == len(convs):
-                plans.append((n.element, ConcatPlan(convs)))
+                masks.append(th)
+            if len({id(t) for t in masks if t is not None}) != sum(t is not None for t in masks):
+                masks = [None] * len(masks)
+            if not (all(c is not None for c in convs) and len({id(c) for c in convs}) == len(convs)):
+                convs = [None] * len(convs)  # never armed: only the training backward's masks are used
+                if all(t is None for t in masks):
+                    continue
+            plans.append((n.element, ConcatPlan(convs, masks)))
         return plans
 
     def updateOutput(self, input):
@@ -172,13 +183,17 @@ class Graph(Container):
         self._node_inputs = {}
         plans = ()
         first = input if isinstance(input, torch.Tensor) else None
-        if not self.train and first is not None and first.is_cuda:
+        if first is not None and first.is_cuda and (not self.train or _concat_train()):
             if getattr(self, "_plans", None) is None:
                 self._plans = self._concat_plans()
             plans = self._plans
         key = tuple(first.shape) if first is not None else None
+        self._train_plans = plans if self.train else ()
+        # (training: the joins see bf16 activations when the graph input is bf16 or is cast to it)
+        bf16 = self.train and plans and (first.dtype == torch.bfloat16 or Engine.compute_dtype() == torch.bfloat16)
         for join, plan in plans:
-            join._planned = plan.arm(key, first)
+            join._planned = plan.arm(key, first, self.train, bf16)
+            join._mask_srcs = plan.masks if self.train else None
         try:
             for n in self.forward_order:
                 if n._id in feeds:
@@ -203,26 +218,44 @@ class Graph(Container):
         else:
             for i, o in enumerate(self.outputs_nodes):
                 grads[o._id] = _add_act(grads.get(o._id), gradOutput[i + 1])
-        for n in reversed(self.forward_order):
-            g = grads.get(n._id)
-            if g is None:
-                continue
-            x = self._node_inputs[n._id]
-            gi = call(n.element, x, g)
-            if n.element.get_name() in self._stop_grad:
-                continue
-            if not n.prev_nodes:
-                grads[("in", n._id)] = gi
-                continue
-            if len(n.prev_nodes) == 1:
-                p, idx = n.prev_nodes[0], n.prev_index[0]
-                grads[p._id] = self._acc(grads.get(p._id), gi, idx, p)
-            else:
-                for k, (p, idx) in enumerate(zip(n.prev_nodes, n.prev_index)):
-                    grads[p._id] = self._acc(grads.get(p._id), gi[k + 1], idx, p)
+        # whole-activity gradients of a node wait as a list and are summed when its turn comes: one
+        # or two in arrival order through _add_act, three or more device tensors in one launch
+        pend = {}
+        try:
+            for n in reversed(self.forward_order):
+                g = grads.get(n._id)
+                if n._id in pend:
+                    g = _sum_acts(([g] if g is not None else []) + pend.pop(n._id))
+                if g is None:
+                    continue
+                x = self._node_inputs[n._id]
+                gi = call(n.element, x, g)
+                if n.element.get_name() in self._stop_grad:
+                    continue
+                if not n.prev_nodes:
+                    grads[("in", n._id)] = gi
+                    continue
+                if len(n.prev_nodes) == 1:
+                    p, idx = n.prev_nodes[0], n.prev_index[0]
+                    self._defer(grads, pend, p, idx, gi)
+                else:
+                    for k, (p, idx) in enumerate(zip(n.prev_nodes, n.prev_index)):
+                        self._defer(grads, pend, p, idx, gi[k + 1])
+        finally:
+            # a one-shot flag a join set on a producer whose backward did not run (stopGradient)
+            for _, plan in getattr(self, "_train_plans", ()):
+                for t in plan.masks:
+                    if t is not None:
+                        t.__dict__.pop("_premasked", None)
         if len(self.inputs) == 1:
             return grads.get(("in", self.inputs[0]._id))
         return Table(*[grads.get(("in", n._id)) for n in self.inputs])
+
+    def _defer(self, grads, pend, p, idx, g):
+        if idx:
+            grads[p._id] = self._acc(grads.get(p._id), g, idx, p)
+        else:
+            pend.setdefault(p._id, []).append(g)
 
     def _acc(self, cur, g, idx, p):
         if idx:

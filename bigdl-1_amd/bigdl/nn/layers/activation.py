@@ -43,6 +43,10 @@ class Threshold(TensorModule):
 
     def updateGradInput(self, input, gradOutput):
         if self._passthrough == "mask":
+            if self.__dict__.pop("_premasked", False):
+                # one shot: the join this ReLU feeds applied the mask while splitting its gradient
+                # (ops.concat_split_backward); set per backward by Concat / JoinTable, cleared here
+                return gradOutput
             # the producer applied this ReLU in its epilogue: input is already ReLU(x), and
             # ReLU(x) > 0 ⇔ x > 0, so the mask comes from it
             return ops.relu_backward(gradOutput, input, 0.0)

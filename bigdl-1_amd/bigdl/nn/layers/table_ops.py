@@ -204,13 +204,47 @@ class JoinTable(TensorModule):
         big, self._planned = self._planned, None
         if big is not None and d == 1 and _tiles_channels(big, ts):
             return big
+        if self.train and d == 1 and ts[0].is_cuda:
+            from ..containers import _concat_train, _native_join
+            y = _native_join(ts) if _concat_train() else None
+            if y is not None:
+                return y
         if ts[0].is_cuda and ts[0].dim() == 4 and d == 1:
             return torch.cat(ts, d).contiguous(memory_format=torch.channels_last)
         return torch.cat(ts, d)
 
+    #: per input, the mask-``Threshold`` that produced it or None (set by the owning Graph for a
+    #: training forward): the backward applies those ReLU masks while it splits the gradient
+    _mask_srcs = None
+
+    def _native_backward(self, ts, d, gradOutput):
+        """Training on the device: split + the producers' ReLU masks (from this join's own output)
+        in one launch; the masked producers are told, once, to pass their gradient through."""
+        if not (self.train and d == 1 and isinstance(gradOutput, torch.Tensor) and gradOutput.is_cuda):
+            return None
+        from ..containers import _concat_train, _native_split
+        if not _concat_train():
+            return None
+        y, srcs = self.output, self._mask_srcs
+        ok = (isinstance(y, torch.Tensor) and y.shape == gradOutput.shape and y.dtype == gradOutput.dtype
+              and srcs is not None and len(srcs) == len(ts))
+        # a producer is masked only when its latest output IS this join's input
+        ths = [s if (ok and s is not None and s._passthrough == "mask" and s.output is t) else None
+               for s, t in zip(srcs if ok else [None] * len(ts), ts)]
+        parts = _native_split(gradOutput, y if ok else None, self._sizes, [t is not None for t in ths])
+        if parts is None:
+            return None
+        for t in ths:
+            if t is not None:
+                t._premasked = True
+        return Table(*parts)
+
     def updateGradInput(self, input, gradOutput):
         ts = list(input)
         d = self._d(ts[0])
+        gi = self._native_backward(ts, d, gradOutput)
+        if gi is not None:
+            return gi
         parts = torch.split(gradOutput, self._sizes, dim=d)
         gi = Table()
         for i, p in enumerate(parts):

@@ -18,6 +18,7 @@ __all__ = [
     "embedding_forward", "embedding_backward", "dropout_forward", "dropout_backward", "lrn_forward", "lrn_backward",
     "quant_rows", "gemm_i8", "image_crop_flip_norm", "attention_forward", "attention_backward",
     "attention_decode", "lars_sumsq", "lars_step",
+    "concat_forward", "concat_split_backward", "sum_n",
 ]
 
 

@@ -125,6 +125,127 @@ def relu_backward(gy, ref, threshold=0.0):
     return gx
 
 
+# ------------------------------------------------------------------------------------------------ concat (K19)
+_CAT_MAX = 8
+
+
+class _CatPart(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("c0", C.c_int), ("c", C.c_int), ("flag", C.c_int), ("pad_", C.c_int)]
+
+
+class _CatTable(C.Structure):
+    _fields_ = [("part", _CatPart * _CAT_MAX), ("n", C.c_int), ("lo", C.c_int), ("span", C.c_int), ("ctot", C.c_int)]
+
+
+class _SumPtrs(C.Structure):
+    _fields_ = [("p", C.c_void_p * _CAT_MAX), ("n", C.c_int), ("pad_", C.c_int)]
+
+
+def _cat_tables(parts, sizes, flags, ctot):
+    """One part table per launch: at most 8 parts each, over disjoint consecutive channel ranges."""
+    tabs, c0 = [], 0
+    for i in range(0, len(parts), _CAT_MAX):
+        t = _CatTable()
+        t.lo = c0
+        for k, (p, c, f) in enumerate(zip(parts[i:i + _CAT_MAX], sizes[i:i + _CAT_MAX], flags[i:i + _CAT_MAX])):
+            t.part[k].p, t.part[k].c0, t.part[k].c, t.part[k].flag = p.data_ptr(), c0, c, int(bool(f))
+            c0 += c
+        t.n, t.span, t.ctot = min(_CAT_MAX, len(parts) - i), c0 - t.lo, ctot
+        tabs.append(t)
+    return tabs
+
+
+def _cat_like(t, c):
+    """A dense tensor shaped like ``t`` with ``c`` channels (NHWC for 4-D)."""
+    if t.dim() == 4:
+        return torch.empty((t.shape[0], c, t.shape[2], t.shape[3]), dtype=t.dtype, device=t.device,
+                           memory_format=torch.channels_last)
+    return torch.empty((t.shape[0], c), dtype=t.dtype, device=t.device)
+
+
+def _cat_geom(t, sizes):
+    """(M, vector width, dtype code) when ``sizes`` channels of ``t``'s dtype can be moved in 16-B
+    chunks of a rows x channels view, else None."""
+    if t.dtype not in (_bf16, _f32) or not t.is_cuda:
+        return None
+    w = 8 if t.dtype == _bf16 else 4
+    if not sizes or any(c <= 0 or c % w for c in sizes) or sum(sizes) >= 2 ** 31:
+        return None
+    m = t.numel() // t.shape[1] if t.shape[1] else 0
+    if m <= 0:
+        return None
+    return m, w, 0 if t.dtype == _bf16 else 1
+
+
+@register("concat_forward")
+def concat_forward(x0, rest=()):
+    xs = [x0, *rest]
+    if any(not isinstance(t, torch.Tensor) or t.dtype != x0.dtype or t.device != x0.device or t.dim() != x0.dim()
+           for t in xs) or x0.dim() not in (2, 4):
+        return NotImplemented
+    if any(t.shape[0] != x0.shape[0] or t.shape[2:] != x0.shape[2:] or _rows_c(t) is None or not _al16(t)
+           for t in xs):
+        return NotImplemented
+    sizes = [int(t.shape[1]) for t in xs]
+    g = _cat_geom(x0, sizes)
+    if g is None:
+        return NotImplemented
+    M, _, code = g
+    y = _cat_like(x0, sum(sizes))
+    if not _al16(y):
+        return NotImplemented
+    for t in _cat_tables(xs, sizes, [0] * len(xs), sum(sizes)):
+        check(_lib().bigdl_concat_fwd(C.byref(t), ptr(y), _ll(M), C.c_int(code), _s()), "concat_fwd")
+    return y
+
+
+@register("concat_split_backward")
+def concat_split_backward(gy, y, sizes, masks=None):
+    sizes = [int(c) for c in sizes]
+    masks = [bool(m) for m in masks] if masks is not None else [False] * len(sizes)
+    if len(masks) != len(sizes) or gy.dim() not in (2, 4) or _rows_c(gy) is None or not _al16(gy):
+        return NotImplemented
+    if sum(sizes) != gy.shape[1]:
+        return NotImplemented
+    g = _cat_geom(gy, sizes)
+    if g is None:
+        return NotImplemented
+    M, _, code = g
+    if any(masks):
+        if not (isinstance(y, torch.Tensor) and y.dtype == gy.dtype and y.device == gy.device and y.shape == gy.shape
+                and y.stride() == gy.stride() and _rows_c(y) is not None and _al16(y)):
+            return NotImplemented
+    else:
+        y = None
+    outs = [_cat_like(gy, c) for c in sizes]
+    if not all(_al16(o) for o in outs):
+        return NotImplemented
+    for t in _cat_tables(outs, sizes, masks, sum(sizes)):
+        check(_lib().bigdl_concat_split_bwd(C.byref(t), ptr(gy), ptr(y), _ll(M), C.c_int(code), _s()),
+              "concat_split_bwd")
+    return outs
+
+
+@register("sum_n")
+def sum_n(a0, rest=()):
+    ts = [a0, *rest]
+    if not 2 <= len(ts) <= _CAT_MAX or a0.dtype not in (_bf16, _f32):
+        return NotImplemented
+    if any(not isinstance(t, torch.Tensor) or t.dtype != a0.dtype or t.device != a0.device or t.shape != a0.shape
+           or t.stride() != a0.stride() or not _dense(t) or not _al16(t) for t in ts):
+        return NotImplemented
+    out = torch.empty_like(a0)
+    if out.stride() != a0.stride() or not _al16(out):
+        return NotImplemented
+    sp = _SumPtrs()
+    for k, t in enumerate(ts):
+        sp.p[k] = t.data_ptr()
+    sp.n = len(ts)
+    check(_lib().bigdl_sum_n(C.byref(sp), ptr(out), _ll(a0.numel()), C.c_int(0 if a0.dtype == _bf16 else 1), _s()),
+          "sum_n")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ batchnorm
 def _bn_ok(x, C_):
     return x.dtype == _bf16 and C_ % 8 == 0 and _al16(x) and C_ <= 8192

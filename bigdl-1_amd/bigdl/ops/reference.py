@@ -42,6 +42,38 @@ def relu_backward(gy: torch.Tensor, y_or_x: torch.Tensor, threshold: float = 0.0
     return gy * (y_or_x > threshold).to(gy.dtype)
 
 
+# ------------------------------------------------------------------------- channel concat (K19)
+def _cl(t: torch.Tensor):
+    """Dense in the layout the native twins produce: channels-last for a 4-D device tensor."""
+    if t.dim() == 4 and t.is_cuda:
+        return t.contiguous(memory_format=torch.channels_last)
+    return t.contiguous()
+
+
+def concat_forward(x0: torch.Tensor, rest=()):
+    """Concatenate ``[x0, *rest]`` along dim 1 (the channels of a 4-D activation or of a 2-D [N, C])."""
+    return _cl(torch.cat([x0, *rest], 1))
+
+
+def concat_split_backward(gy: torch.Tensor, y: Optional[torch.Tensor], sizes, masks=None):
+    """Split ``gy`` along dim 1 into dense parts of ``sizes`` channels; where ``masks[k]`` the part
+    is the gradient through a ReLU whose output is the same slice of ``y`` (the concat's forward
+    output): a select ``y > 0 ? gy : 0``, not a multiply."""
+    masks = list(masks) if masks is not None else [False] * len(sizes)
+    gs = torch.split(gy, list(sizes), 1)
+    ys = torch.split(y, list(sizes), 1) if (y is not None and any(masks)) else [None] * len(gs)
+    return [_cl(torch.where(yk > 0, g, torch.zeros((), dtype=g.dtype, device=g.device)) if m else g)
+            for g, yk, m in zip(gs, ys, masks)]
+
+
+def sum_n(a0: torch.Tensor, rest=()):
+    """``((a0 + r1) + r2) + ...``: left to right, rounded to the storage dtype after every add."""
+    out = a0
+    for t in rest:
+        out = out + t
+    return out
+
+
 # ------------------------------------------------------------------------- convolution
 def conv2d_forward(x, w4, b, stride, pad, dilation=(1, 1), groups=1, relu=False, out=None, res=None, pad_slot=None):
     """``SpatialConvolution.updateOutput`` (``DL/nn/SpatialConvolution.scala:253-362``).

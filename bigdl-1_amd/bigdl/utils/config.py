@@ -94,6 +94,7 @@ _REGISTRY = {
     "bigdl.fusion.convsum": (bool, True, "fuse residual add"),
     "bigdl.fusion.convstats": (bool, True, "conv epilogue emits the following training BN's statistics"),
     "bigdl.fusion.shortcutbn": (bool, True, "a ResNet block's conv->BN shortcut hands its BN output to the fused tail deferred (input + coefficients), applied inside the tail's pass"),
+    "bigdl.concat.train": (bool, True, "native channel concat in training (K19): a Concat / JoinTable whose branches all end in a conv (-> fused ReLU) has them write their channel slices of one shared bf16 NHWC output (zero-copy forward), any other device join runs the one-launch concat kernel, the backward splits the gradient and applies the branches' ReLU masks in one launch, and 3 or more input gradients of a fan-out are summed in one launch. Bit-identical to the torch path it replaces (false = that path)"),
     "bigdl.fusion.bnbwd": (bool, True, "dgrad epilogue applies the producing BN's ReLU mask and its backward reductions"),
     "bigdl.fusion.bnpool": (bool, True, "a training BN + ReLU whose only consumer is a 3x3 stride-2 max-pool (the ResNet stem) hands its output over deferred (bf16 on a GPU): the pool applies BN + ReLU to its window taps on load and the BN backward gathers the pool gradient through the argmax on load - the BN output and the dense pool gradient are never written"),
     "bigdl.fusion.bnprologue": (int, 0, "a BN whose producer is a 1x1 stride-1 conv hands it the input gradient "

@@ -7,6 +7,7 @@
     python tools/bench_configs.py --config inception  # 5: Inception-v1 from Caffe files, batch inference
     python tools/bench_configs.py --config transformer  # Transformer LM 6x512 (native LayerNorm A/B)
     python tools/bench_configs.py --config int8       # VGG16 inference: int8 vs fp32 (bf16x3) vs bf16
+    python tools/bench_configs.py --config inception_train  # Inception-v1 training, bigdl.concat.train A/B
     python tools/bench_configs.py --config all
 
 Every config builds the model exactly as the reference's example/model builder does, uses synthetic
@@ -295,6 +296,74 @@ def bench_inception(args):
                        "load_roundtrip_s": round(load_s, 2), "roundtrip_max_abs_diff": err}}
 
 
+def bench_inception_train(args):
+    """Inception-v1 training, the reference's one published training throughput (920 records/s on
+    16 nodes): ``Inception_v1_NoAuxClassifier`` built and optimized as ``models/inception/Train.scala:62-84``
+    (ClassNLLCriterion; SGD lr 0.01, momentum 0.9, dampening 0, no nesterov, weight decay 1e-4,
+    Poly(0.5, 62000)), synthetic 224² data, batch 256, one GPU.  A/B of ``bigdl.concat.train`` (native
+    concat in training, K19): two optimizers on identical models in one process, the arms alternated
+    ``--repeats`` times; the headline value is the property's default arm."""
+    import copy
+    import statistics
+    import torch
+    from bigdl.utils import config
+    config.set_property("bigdl.compute.dtype", args.dtype)
+    from bigdl.utils.engine import Engine
+    Engine.init()
+    dev = Engine.device()
+    from bigdl import ops
+    from bigdl.models.inception import Inception_v1_NoAuxClassifier
+    from bigdl.nn import ClassNLLCriterion
+    from bigdl.optim import SGD, Poly
+    from bigdl.optim.optimizer import LocalOptimizer
+    from bigdl.dataset import MiniBatch
+    from bigdl.utils.random import RNG
+    RNG.setSeed(5)
+    B = args.batch or 256
+    g = torch.Generator().manual_seed(5)
+    dt = Engine.compute_dtype() if dev.type == "cuda" else torch.float32
+    x = torch.randn(B, 3, 224, 224, generator=g).to(dev).to(dt).contiguous(memory_format=torch.channels_last)
+    y = (torch.randint(0, 1000, (B,), generator=g) + 1).float().to(dev)
+    batch = MiniBatch(x, y)
+    default_on = bool(config.get_property("bigdl.concat.train"))
+    arms = [a for a in ("on", "off") if args.arm in ("both", a)]
+    src = Inception_v1_NoAuxClassifier(1000)
+    opts = {}
+    for arm in arms:
+        sgd = SGD(learningrate=0.01, learningrate_decay=0.0, weightdecay=1e-4, momentum=0.9, dampening=0.0,
+                  nesterov=False, leaningrate_schedule=Poly(0.5, 62000))
+        opts[arm] = LocalOptimizer(copy.deepcopy(src), [batch], ClassNLLCriterion(), sgd, batch_size=B)
+        opts[arm].prepare()
+
+    def run(arm, steps, warmup):
+        config.set_property("bigdl.concat.train", arm == "on")
+        return _time_steps(lambda: opts[arm].train_step(batch), dev, steps, warmup)
+
+    ms = {a: [] for a in arms}
+    loss, fb = {}, {}
+    for a in arms:  # compile phase (kernel selection) and shape recording, untimed
+        ops.reset_fallbacks()
+        run(a, 0, max(args.warmup, 2))
+        # ops that ran the torch reference on device tensors, per arm (calls over the warmup steps)
+        fb[a] = {f"{k[0]} ({k[1]}: {k[2]})": v for k, v in ops.fallback_counts().items()}
+    for _ in range(max(1, args.repeats)):
+        for a in arms:
+            el, l = run(a, args.steps, 1)
+            ms[a].append(round(el / args.steps * 1e3, 3))
+            loss[a] = float(l)
+    config.set_property("bigdl.concat.train", default_on)
+    head = ("on" if default_on else "off") if args.arm == "both" else arms[0]
+    med = {a: statistics.median(v) for a, v in ms.items()}
+    return {"metric": "images/sec Inception-v1 (NoAux) training 1 GPU", "value": round(B / med[head] * 1e3, 1),
+            "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
+            "ms_per_step": med[head], "higher_is_better": True, "dtype": args.dtype, "data": "synthetic",
+            "config": {"model": "Inception_v1_NoAuxClassifier", "global_batch": B, "image_size": 224,
+                       "optimizer": "SGD lr 0.01 momentum 0.9 wd 1e-4 Poly(0.5, 62000)", "headline_arm": head},
+            "concat_train_ms_per_step": ms, "concat_train_median_ms": med,
+            "on_over_off_speedup": round(med["off"] / med["on"], 4) if len(arms) == 2 else None,
+            "reference_records_per_sec_16_nodes": 920, "final_loss": loss, "torch_fallbacks": fb}
+
+
 def bench_resnet_infer(args):
     """ResNet-50 batch inference through the IR lowering (``ConversionUtils.convert``: BN folded
     into the convs, ReLU in the conv epilogues), bf16, random-init weights with non-trivial BN
@@ -556,11 +625,16 @@ def bench_int8(args):
 
 CONFIGS = {"lenet": bench_lenet, "vgg": bench_vgg, "ptb": bench_ptb, "inception": bench_inception,
            "resnet_infer": bench_resnet_infer, "transformer": bench_transformer, "int8": bench_int8}
+# run by name only (``--config all`` keeps the set it always ran)
+EXTRA_CONFIGS = {"inception_train": bench_inception_train}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="all", choices=list(CONFIGS) + ["all"])
+    ap.add_argument("--config", default="all", choices=list(CONFIGS) + list(EXTRA_CONFIGS) + ["all"])
+    ap.add_argument("--repeats", type=int, default=3, help="inception_train: timed runs per arm, arms alternated")
+    ap.add_argument("--arm", default="both", choices=["both", "on", "off"],
+                    help="inception_train: bigdl.concat.train arms to run (one arm: a profiling run)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=0, help="0 = the config's reference default")
@@ -582,7 +656,7 @@ def main():
     _CPROFILE["n"] = args.cprofile
     names = list(CONFIGS) if args.config == "all" else [args.config]
     for n in names:
-        r = CONFIGS[n](args)
+        r = (CONFIGS.get(n) or EXTRA_CONFIGS[n])(args)
         if r is not None:
             print(json.dumps(r), flush=True)
 

@@ -1,5 +1,7 @@
-"""Attribute the non-HIP-kernel work of one ResNet-50 training step (copies, fills, torch
-elementwise) to its Python call sites with torch.profiler (CPU-side op stacks)."""
+"""Attribute the non-HIP-kernel work of one training step (copies, fills, torch elementwise) to its
+Python call sites with torch.profiler (CPU-side op stacks).  ResNet-50 by default;
+``MODEL=inception`` takes Inception-v1 (NoAux) as ``tools/bench_configs.py --config inception_train``
+trains it."""
 import os
 import sys
 import collections
@@ -18,11 +20,17 @@ from bigdl.optim.optimizer import LocalOptimizer
 from bigdl.dataset import MiniBatch
 
 B = int(os.environ.get("B", "64"))
-model = model_init(ResNet(1000, depth=50, dataset=DatasetType.ImageNet))
+if os.environ.get("MODEL", "resnet50") == "inception":
+    from bigdl.models.inception import Inception_v1_NoAuxClassifier
+    from bigdl.nn import ClassNLLCriterion
+    model, crit = Inception_v1_NoAuxClassifier(1000), ClassNLLCriterion()
+    method = SGD(learningrate=0.01, momentum=0.9, dampening=0.0, weightdecay=1e-4)
+else:
+    model, crit = model_init(ResNet(1000, depth=50, dataset=DatasetType.ImageNet)), CrossEntropyCriterion()
+    method = SGD(learningrate=0.1, momentum=0.9, dampening=0.0, nesterov=True, weightdecay=1e-4)
 x = torch.randn(B, 3, 224, 224, device="cuda").to(torch.bfloat16 if DT == "bf16" else torch.float32).contiguous(memory_format=torch.channels_last)
 y = (torch.randint(0, 1000, (B,), device="cuda") + 1).float()
-opt = LocalOptimizer(model, [MiniBatch(x, y)], CrossEntropyCriterion(),
-                     SGD(learningrate=0.1, momentum=0.9, dampening=0.0, nesterov=True, weightdecay=1e-4), batch_size=B)
+opt = LocalOptimizer(model, [MiniBatch(x, y)], crit, method, batch_size=B)
 opt.prepare()
 for _ in range(3):
     opt.train_step(MiniBatch(x, y))
