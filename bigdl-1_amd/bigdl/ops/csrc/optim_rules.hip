@@ -1,0 +1,220 @@
+// Fused updates of the elementwise optimisation methods that have no kernel of their own in
+// elementwise.hip: RMSprop, Adadelta, Adamax, Ftrl, and Adam with a bf16 gradient.
+//
+// ONE streaming kernel (k_optim), templated on an update rule and on the gradient type, with the
+// structure of k_adagrad: grid-stride float4 body, the n & 3 tail on block 0, long long indices,
+// a bf16 gradient (the DistriOptimizer's reduce-scatter wire shard) widened on load, and the
+// optional bf16 shadow written from the new weight as one uint2.  HBM-bound: 16 B per lane per
+// access, grid capped at 2048 blocks of 256 (cdna_hip_programming.md Guideline 11).
+//
+// A rule is a struct of its hyper-parameters (by value in the kernel arguments) with
+//   NS                     number of fp32 state tensors (1 or 2)
+//   step(w, g, a, b)       the per-element update over the weight, the raw gradient and the states
+// Every rule is the torch form of its class in optim/optim_method.py (the CPU path and the
+// oracle), term for term; constants such as 1 - decay are formed on the host in double, as the
+// torch form does.  Plain IEEE division and sqrtf only: Adamax's default eps = 1e-38 is a subnormal
+// fp32 and must survive (no fast-math, no reciprocal approximations).
+#include "common.h"
+
+__device__ __forceinline__ float ag_ld(const float* g, long long e) { return g[e]; }
+__device__ __forceinline__ float ag_ld(const bf16_t* g, long long e) { return bf2f(g[e]); }
+__device__ __forceinline__ void ag_ld4(const float* g, long long i, float (&o)[4]) {
+  const float4 G = reinterpret_cast<const float4*>(g)[i];
+  o[0] = G.x; o[1] = G.y; o[2] = G.z; o[3] = G.w;
+}
+__device__ __forceinline__ void ag_ld4(const bf16_t* g, long long i, float (&o)[4]) {
+  const uint2 u = reinterpret_cast<const uint2*>(g)[i];
+  o[0] = __uint_as_float(u.x << 16); o[1] = __uint_as_float(u.x & 0xFFFF0000u);
+  o[2] = __uint_as_float(u.y << 16); o[3] = __uint_as_float(u.y & 0xFFFF0000u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rules
+// ------------------------------------------------------------------------------------------------
+// RMSprop (DL/optim/RMSprop.scala): s = dr·s + (1-dr)·g'² ; w -= clr·g' / (sqrt(s) + eps)
+struct RmspropRule {
+  static constexpr int NS = 1;
+  float scale, clr, dr, omdr, eps;
+  __device__ __forceinline__ void step(float& w, float g, float& s, float&) const {
+    const float gg = g * scale;
+    s = dr * s + omdr * gg * gg;
+    w -= clr * (gg / (sqrtf(s) + eps));
+  }
+};
+
+// Adadelta (DL/optim/Adadelta.scala): v = dr·v + (1-dr)·g'² ; upd = sqrt(d+eps)/sqrt(v+eps)·g' ;
+// d = dr·d + (1-dr)·upd² ; w -= upd
+struct AdadeltaRule {
+  static constexpr int NS = 2;
+  float scale, dr, omdr, eps;
+  __device__ __forceinline__ void step(float& w, float g, float& v, float& d) const {
+    const float gg = g * scale;
+    v = dr * v + omdr * gg * gg;
+    const float upd = sqrtf(d + eps) / sqrtf(v + eps) * gg;
+    d = dr * d + omdr * upd * upd;
+    w -= upd;
+  }
+};
+
+// Adamax (DL/optim/Adamax.scala): m = b1·m + (1-b1)·g' ; u = max(b2·u, |g'| + eps) ;
+// w -= step·m/u, step = lr / (1 - b1^t) from the host.  An element whose gradient was 0 at every
+// step has m = 0 and u = eps (subnormal by default): m/u = 0 exactly, so w keeps its bits.
+struct AdamaxRule {
+  static constexpr int NS = 2;
+  float scale, stepsz, b1, omb1, b2, eps;
+  __device__ __forceinline__ void step(float& w, float g, float& m, float& u) const {
+    const float gg = g * scale;
+    m = b1 * m + omb1 * gg;
+    u = fmaxf(b2 * u, fabsf(gg) + eps);
+    w -= stepsz * (m / u);
+  }
+};
+
+// FTRL-proximal in the form of Ftrl._update (the raw gradient squared goes into the accumulator,
+// as TensorFlow's FtrlV2): gs = g' + 2·l2s·w ; acc' = acc + g'² ; σ = (acc'^p - acc^p)/lr ;
+// lin += gs - σ·w ; quad = acc'^p/lr + 2·l2 ; w = |lin| > l1 ? -(|lin| - l1)·sign(lin)/quad : 0.
+// PM selects x^p: 0 = sqrtf (p = 0.5, the default), 1 = the constant 1 (p = 0), 2 = powf.
+template <int PM>
+struct FtrlRule {
+  static constexpr int NS = 2;
+  float scale, lr, p, l1, two_l2, two_l2s;
+  __device__ __forceinline__ float pw(float x) const {
+    if (PM == 0) return sqrtf(x);
+    if (PM == 1) return 1.f;
+    return powf(x, p);
+  }
+  __device__ __forceinline__ void step(float& w, float g, float& acc, float& lin) const {
+    const float gg = g * scale;
+    const float gs = two_l2s > 0.f ? gg + two_l2s * w : gg;
+    const float na = acc + gg * gg;
+    const float nap = pw(na);
+    const float sigma = (nap - pw(acc)) / lr;
+    lin += gs - sigma * w;
+    const float quad = nap / lr + two_l2;
+    const float al = fabsf(lin);
+    const float sgn = lin > 0.f ? 1.f : (lin < 0.f ? -1.f : 0.f);
+    w = al > l1 ? -((al - l1) * sgn) / quad : 0.f;
+    acc = na;
+  }
+};
+
+// Adam with k_adam's arithmetic (elementwise.hip), for the bf16 gradient instance
+struct AdamRule {
+  static constexpr int NS = 2;
+  float scale, step_size, b1, b2, eps, wd;
+  __device__ __forceinline__ void step(float& w, float g, float& m, float& v) const {
+    const float gg = g * scale + wd * w;
+    m = b1 * m + (1.f - b1) * gg;
+    v = b2 * v + (1.f - b2) * gg * gg;
+    w -= step_size * m / (sqrtf(v) + eps);
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
+// the kernel: w, s0, s1 16-B aligned, g 16-B (fp32) or 8-B (bf16), shadow 8-B (host-checked);
+// s1 is not touched when the rule has one state
+// ------------------------------------------------------------------------------------------------
+template <typename R, typename G>
+__global__ void k_optim(R r, float* __restrict__ w, const G* __restrict__ g, float* __restrict__ s0,
+                        float* __restrict__ s1, bf16_t* __restrict__ shadow, long long n4, int tail) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  if (blockIdx.x == 0 && threadIdx.x < tail) {
+    const long long e = n4 * 4 + threadIdx.x;
+    float nw = w[e], a = s0[e], b = 0.f;
+    if (R::NS > 1) b = s1[e];
+    r.step(nw, ag_ld(g, e), a, b);
+    w[e] = nw;
+    s0[e] = a;
+    if (R::NS > 1) s1[e] = b;
+    if (shadow) shadow[e] = f2bf(nw);
+  }
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 W = reinterpret_cast<float4*>(w)[i];
+    const float4 A = reinterpret_cast<float4*>(s0)[i];
+    float wv[4] = {W.x, W.y, W.z, W.w}, gv[4], av[4] = {A.x, A.y, A.z, A.w}, bv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (R::NS > 1) {
+      const float4 B = reinterpret_cast<float4*>(s1)[i];
+      bv[0] = B.x; bv[1] = B.y; bv[2] = B.z; bv[3] = B.w;
+    }
+    ag_ld4(g, i, gv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r.step(wv[k], gv[k], av[k], bv[k]);
+    reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
+    reinterpret_cast<float4*>(s0)[i] = make_float4(av[0], av[1], av[2], av[3]);
+    if (R::NS > 1) reinterpret_cast<float4*>(s1)[i] = make_float4(bv[0], bv[1], bv[2], bv[3]);
+    if (shadow) {
+      const uint32_t lo = (uint32_t)f2bf(wv[0]) | ((uint32_t)f2bf(wv[1]) << 16);
+      const uint32_t hi = (uint32_t)f2bf(wv[2]) | ((uint32_t)f2bf(wv[3]) << 16);
+      reinterpret_cast<uint2*>(shadow)[i] = make_uint2(lo, hi);
+    }
+  }
+}
+
+template <typename R, typename G>
+static int optim_launch(const R& r, float* w, const G* g, float* s0, float* s1, bf16_t* shadow, long long n,
+                        hipStream_t s) {
+  if (n <= 0) return 0;
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL((k_optim<R, G>), dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, r, w, g, s0, s1,
+                     shadow, n4, (int)(n & 3));
+  BIGDL_CHECK_LAUNCH();
+}
+
+template <typename G>
+static int ftrl_launch(float* w, const G* g, float* acc, float* lin, bf16_t* shadow, long long n, float lr, float p,
+                       float l1, float two_l2, float two_l2s, float scale, hipStream_t s) {
+  if (p == 0.5f) return optim_launch(FtrlRule<0>{scale, lr, p, l1, two_l2, two_l2s}, w, g, acc, lin, shadow, n, s);
+  if (p == 0.f) return optim_launch(FtrlRule<1>{scale, lr, p, l1, two_l2, two_l2s}, w, g, acc, lin, shadow, n, s);
+  return optim_launch(FtrlRule<2>{scale, lr, p, l1, two_l2, two_l2s}, w, g, acc, lin, shadow, n, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// entry points: n elements; the _g16 twins take a bf16 gradient
+// ------------------------------------------------------------------------------------------------
+BIGDL_EXPORT int bigdl_rmsprop(float* w, const float* g, float* sq, bf16_t* shadow, long long n, float clr, float dr,
+                               float omdr, float eps, float scale, hipStream_t s) {
+  return optim_launch(RmspropRule{scale, clr, dr, omdr, eps}, w, g, sq, (float*)nullptr, shadow, n, s);
+}
+
+BIGDL_EXPORT int bigdl_rmsprop_g16(float* w, const bf16_t* g, float* sq, bf16_t* shadow, long long n, float clr,
+                                   float dr, float omdr, float eps, float scale, hipStream_t s) {
+  return optim_launch(RmspropRule{scale, clr, dr, omdr, eps}, w, g, sq, (float*)nullptr, shadow, n, s);
+}
+
+BIGDL_EXPORT int bigdl_adadelta(float* w, const float* g, float* v, float* d, bf16_t* shadow, long long n, float dr,
+                                float omdr, float eps, float scale, hipStream_t s) {
+  return optim_launch(AdadeltaRule{scale, dr, omdr, eps}, w, g, v, d, shadow, n, s);
+}
+
+BIGDL_EXPORT int bigdl_adadelta_g16(float* w, const bf16_t* g, float* v, float* d, bf16_t* shadow, long long n,
+                                    float dr, float omdr, float eps, float scale, hipStream_t s) {
+  return optim_launch(AdadeltaRule{scale, dr, omdr, eps}, w, g, v, d, shadow, n, s);
+}
+
+// step = lr / (1 - b1^t)
+BIGDL_EXPORT int bigdl_adamax(float* w, const float* g, float* m, float* u, bf16_t* shadow, long long n, float step,
+                              float b1, float omb1, float b2, float eps, float scale, hipStream_t s) {
+  return optim_launch(AdamaxRule{scale, step, b1, omb1, b2, eps}, w, g, m, u, shadow, n, s);
+}
+
+BIGDL_EXPORT int bigdl_adamax_g16(float* w, const bf16_t* g, float* m, float* u, bf16_t* shadow, long long n,
+                                  float step, float b1, float omb1, float b2, float eps, float scale, hipStream_t s) {
+  return optim_launch(AdamaxRule{scale, step, b1, omb1, b2, eps}, w, g, m, u, shadow, n, s);
+}
+
+// p = -learningRatePower; two_l2 = 2·l2, two_l2s = 2·l2Shrinkage
+BIGDL_EXPORT int bigdl_ftrl(float* w, const float* g, float* acc, float* lin, bf16_t* shadow, long long n, float lr,
+                            float p, float l1, float two_l2, float two_l2s, float scale, hipStream_t s) {
+  return ftrl_launch(w, g, acc, lin, shadow, n, lr, p, l1, two_l2, two_l2s, scale, s);
+}
+
+BIGDL_EXPORT int bigdl_ftrl_g16(float* w, const bf16_t* g, float* acc, float* lin, bf16_t* shadow, long long n,
+                                float lr, float p, float l1, float two_l2, float two_l2s, float scale, hipStream_t s) {
+  return ftrl_launch(w, g, acc, lin, shadow, n, lr, p, l1, two_l2, two_l2s, scale, s);
+}
+
+// bigdl_adam with a bf16 gradient (g 8-B aligned)
+BIGDL_EXPORT int bigdl_adam_g16(float* w, const bf16_t* g, float* m, float* v, bf16_t* shadow, long long n,
+                                float step_size, float b1, float b2, float eps, float wd, float scale, hipStream_t s) {
+  return optim_launch(AdamRule{scale, step_size, b1, b2, eps, wd}, w, g, m, v, shadow, n, s);
+}

@@ -9,6 +9,7 @@ static const char* kOps[] = {
     "avgpool_bwd", "softmax", "class_nll", "spmm_csr", "trunc_bf16", "nchw_to_nhwc_bf16", "nms", "roi_align", "vml_unary", "vml_binary", "reduce", "depthwise", "layernorm", "adam_dev", "attention", "stream_probe", "resize_bilinear", "pool3d", "split_bf16x3", "conv_fwd_f32out", "bn32",
     "lars_sumsq", "lars_fold", "lars_sgd",
     "concat_fwd", "concat_split_bwd", "sum_n",
+    "rmsprop", "adadelta", "adamax", "ftrl", "adam_g16",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

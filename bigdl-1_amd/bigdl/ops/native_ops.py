@@ -1931,17 +1931,24 @@ def lars_step(w, g, v, table, sums, hyper, grad_scale=1.0, shadow=None, c0=0, c1
 
 @register("adam_step")
 def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None):
+    """Fused Adam; ``g`` is fp32 or bf16 (the bf16 wire shard, widened on load: bigdl_adam_g16)."""
     import math
     F3.mark_dirty(w)
     n = w.numel()
-    if w.dtype != _f32 or g.dtype != _f32 or not _vec_ok(w, g, m, v, n=n):
-        return NotImplemented
-    if shadow is not None and not (shadow.dtype == _bf16 and shadow.is_contiguous() and shadow.numel() == n
-                                   and shadow.data_ptr() % 8 == 0):
-        return NotImplemented
+    if g.dtype == _bf16:
+        if not _rule_ok(w, g, (m, v), shadow):
+            return NotImplemented
+        fn = _lib().bigdl_adam_g16
+    else:
+        if w.dtype != _f32 or g.dtype != _f32 or not _vec_ok(w, g, m, v, n=n):
+            return NotImplemented
+        if shadow is not None and not (shadow.dtype == _bf16 and shadow.is_contiguous() and shadow.numel() == n
+                                       and shadow.data_ptr() % 8 == 0):
+            return NotImplemented
+        fn = _lib().bigdl_adam
     step_size = lr * math.sqrt(1 - beta2 ** step) / (1 - beta1 ** step)
-    check(_lib().bigdl_adam(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(n), _f(step_size), _f(beta1), _f(beta2),
-                            _f(eps), _f(weight_decay), _f(grad_scale), _s()), "adam")
+    check(fn(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(n), _f(step_size), _f(beta1), _f(beta2),
+             _f(eps), _f(weight_decay), _f(grad_scale), _s()), "adam")
     return w
 
 
@@ -1985,6 +1992,74 @@ def adagrad_step(w, g, s, lr, lr_decay, n, weight_decay=0.0, grad_scale=1.0, sha
     fn = _lib().bigdl_adagrad_g16 if g16 else _lib().bigdl_adagrad
     check(fn(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(numel), _f(clr), ptr(dev_n), _f(lr), _f(lr_decay),
              _f(weight_decay), _f(grad_scale), _s()), "adagrad")
+    return w
+
+
+def _rule_ok(w, g, states, shadow):
+    """Operand contract of the rule kernels (csrc/optim_rules.hip): ``w`` and the states fp32, device,
+    contiguous, equally long, 16-B aligned; ``g`` fp32 (16-B aligned) or bf16 (8-B aligned);
+    ``shadow`` None or bf16, contiguous, 8-B aligned."""
+    n = w.numel()
+    if w.dtype != _f32 or any(s.dtype != _f32 for s in states) or not _vec_ok(w, *states, n=n):
+        return False
+    if g.dtype == _bf16:
+        if not (g.is_cuda and g.is_contiguous() and g.numel() == n and g.data_ptr() % 8 == 0):
+            return False
+    elif g.dtype != _f32 or not _vec_ok(g, n=n):
+        return False
+    return shadow is None or (shadow.is_cuda and shadow.dtype == _bf16 and shadow.is_contiguous()
+                              and shadow.numel() == n and shadow.data_ptr() % 8 == 0)
+
+
+@register("rmsprop_step")
+def rmsprop_step(w, g, s, clr, decay_rate, eps, grad_scale=1.0, shadow=None):
+    """Fused RMSprop update (bigdl_rmsprop): s = dr·s + (1-dr)·g'², w -= clr·g'/(sqrt(s) + eps) with
+    g' = grad_scale·g, one pass over w, g, s and the bf16 shadow; ``g`` fp32 or the bf16 wire shard."""
+    F3.mark_dirty(w)
+    if not _rule_ok(w, g, (s,), shadow):
+        return NotImplemented
+    fn = _lib().bigdl_rmsprop_g16 if g.dtype == _bf16 else _lib().bigdl_rmsprop
+    check(fn(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(w.numel()), _f(clr), _f(decay_rate), _f(1 - decay_rate),
+             _f(eps), _f(grad_scale), _s()), "rmsprop")
+    return w
+
+
+@register("adadelta_step")
+def adadelta_step(w, g, v, d, decay_rate, eps, grad_scale=1.0, shadow=None):
+    """Fused Adadelta update (bigdl_adadelta) over w, g, the squared-gradient average ``v`` and the
+    squared-update average ``d``."""
+    F3.mark_dirty(w)
+    if not _rule_ok(w, g, (v, d), shadow):
+        return NotImplemented
+    fn = _lib().bigdl_adadelta_g16 if g.dtype == _bf16 else _lib().bigdl_adadelta
+    check(fn(ptr(w), ptr(g), ptr(v), ptr(d), ptr(shadow), _ll(w.numel()), _f(decay_rate), _f(1 - decay_rate),
+             _f(eps), _f(grad_scale), _s()), "adadelta")
+    return w
+
+
+@register("adamax_step")
+def adamax_step(w, g, m, u, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=None):
+    """Fused Adamax update (bigdl_adamax); ``step`` is the 1-based iteration, the bias-corrected
+    rate lr / (1 - beta1^step) is formed here.  ``eps`` may be a subnormal fp32 (the default 1e-38)."""
+    F3.mark_dirty(w)
+    if not _rule_ok(w, g, (m, u), shadow):
+        return NotImplemented
+    fn = _lib().bigdl_adamax_g16 if g.dtype == _bf16 else _lib().bigdl_adamax
+    check(fn(ptr(w), ptr(g), ptr(m), ptr(u), ptr(shadow), _ll(w.numel()), _f(lr / (1 - beta1 ** step)), _f(beta1),
+             _f(1 - beta1), _f(beta2), _f(eps), _f(grad_scale), _s()), "adamax")
+    return w
+
+
+@register("ftrl_step")
+def ftrl_step(w, g, accum, linear, lr, lr_power, l1, l2, l2_shrinkage, grad_scale=1.0, shadow=None):
+    """Fused FTRL-proximal update (bigdl_ftrl) in the form of ``Ftrl._update``; ``lr_power`` is the
+    (non-positive) learningRatePower."""
+    F3.mark_dirty(w)
+    if not _rule_ok(w, g, (accum, linear), shadow):
+        return NotImplemented
+    fn = _lib().bigdl_ftrl_g16 if g.dtype == _bf16 else _lib().bigdl_ftrl
+    check(fn(ptr(w), ptr(g), ptr(accum), ptr(linear), ptr(shadow), _ll(w.numel()), _f(lr), _f(-lr_power), _f(l1),
+             _f(2 * l2), _f(2 * l2_shrinkage), _f(grad_scale), _s()), "ftrl")
     return w
 
 

@@ -654,7 +654,7 @@ def sgd_step(w, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_s
 
 def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None):
     """``DL/optim/Adam.scala``: bias-corrected Adam."""
-    gg = g * grad_scale
+    gg = g.float() * grad_scale  # a bf16-wire gradient shard is consumed directly
     if weight_decay != 0:
         gg = gg + weight_decay * w
     m.mul_(beta1).add_(gg, alpha=1 - beta1)

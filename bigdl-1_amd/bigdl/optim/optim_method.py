@@ -7,7 +7,9 @@ are attributes (``loadFromTable`` / ``getHyperParameter`` / ``updateHyperParamet
 Device path: ``x``/``grad`` are flat fp32 arenas (or this rank's shard of one); the whole update is
 ONE fused HIP kernel over the flat buffer (``ops.sgd_step`` / ``ops.adam_step``, K22) that also
 folds in the 1/N gradient averaging (``grad_scale``) and writes the bf16 shadow copy used by the
-next forward.  ``SGD``'s learning rate follows the reference's negative ``clr`` convention
+next forward.  Adagrad, and — under ``bigdl.optim.fused`` — Adamax, Adadelta, RMSprop and Ftrl
+update the same way (``ops/csrc/optim_rules.hip``); their torch forms below stay the CPU path and
+the kernels' oracle.  ``SGD``'s learning rate follows the reference's negative ``clr`` convention
 (``SGD.scala:61-124``): schedules produce ``currentRate = -lr``.
 """
 from __future__ import annotations
@@ -18,6 +20,7 @@ from typing import Callable, List, Optional
 import torch
 
 from .. import ops
+from ..utils import config
 from ..utils.table import Table
 
 
@@ -445,6 +448,8 @@ class SGD(OptimMethod):
 
 # ----------------------------------------------------------------------------------------- Adam family
 class Adam(OptimMethod):
+    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
+
     def __init__(self, learningrate=1e-3, learningrate_decay=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8,
                  bigdl_type="float"):
         super().__init__()
@@ -545,7 +550,15 @@ def _write_shadow(shadow, x):
             shadow.copy_(x)
 
 
+def _fused(x, op):
+    """True when the update of ``x`` goes to the one-pass rule kernel ``op`` (csrc/optim_rules.hip):
+    device weights, ``bigdl.optim.fused`` on and the kernel loaded."""
+    return x.is_cuda and config.get_property("bigdl.optim.fused") and ops.native_has(op)
+
+
 class Adamax(_Elementwise):
+    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
+
     def __init__(self, learningrate=0.002, beta1=0.9, beta2=0.999, epsilon=1e-38, bigdl_type="float"):
         super().__init__()
         self.learningRate, self.beta1, self.beta2, self.epsilon = learningrate, beta1, beta2, epsilon
@@ -556,8 +569,14 @@ class Adamax(_Elementwise):
         self._state_tensor("u", x)
 
     def _update(self, x, g, sl, shadow):
-        g = g * self.grad_scale
         m, u = self.state["m"][sl], self.state["u"][sl]
+        if _fused(x, "adamax_step"):
+            # one fused pass (k_optim<AdamaxRule>) over w, g, m, u and the bf16 shadow
+            r = ops.native_ops.adamax_step(x, g, m, u, self.learningRate, self.beta1, self.beta2, self.epsilon,
+                                           self._t, self.grad_scale, shadow)
+            if r is not NotImplemented:
+                return
+        g = g.float() * self.grad_scale
         m.mul_(self.beta1).add_(g, alpha=1 - self.beta1)
         torch.maximum(u * self.beta2, g.abs() + self.epsilon, out=u)
         x.addcdiv_(m, u, value=-self.learningRate / (1 - self.beta1 ** self._t))
@@ -627,6 +646,8 @@ class Adagrad(_Elementwise):
 
 
 class Adadelta(_Elementwise):
+    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
+
     def __init__(self, decayrate=0.9, epsilon=1e-10, bigdl_type="float"):
         super().__init__()
         self.decayRate, self.epsilon = decayrate, epsilon
@@ -636,8 +657,13 @@ class Adadelta(_Elementwise):
         self._state_tensor("delta", x)
 
     def _update(self, x, g, sl, shadow):
-        g = g * self.grad_scale
         v, d = self.state["paramVariance"][sl], self.state["delta"][sl]
+        if _fused(x, "adadelta_step"):
+            # one fused pass (k_optim<AdadeltaRule>) over w, g, both averages and the bf16 shadow
+            r = ops.native_ops.adadelta_step(x, g, v, d, self.decayRate, self.epsilon, self.grad_scale, shadow)
+            if r is not NotImplemented:
+                return
+        g = g.float() * self.grad_scale
         v.mul_(self.decayRate).addcmul_(g, g, value=1 - self.decayRate)
         upd = (d + self.epsilon).sqrt() / (v + self.epsilon).sqrt() * g
         d.mul_(self.decayRate).addcmul_(upd, upd, value=1 - self.decayRate)
@@ -646,6 +672,8 @@ class Adadelta(_Elementwise):
 
 
 class RMSprop(_Elementwise):
+    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
+
     def __init__(self, learningrate=1e-2, learningrate_decay=0.0, decayrate=0.99, epsilon=1e-8, bigdl_type="float"):
         super().__init__()
         self.learningRate, self.learningRateDecay = learningrate, learningrate_decay
@@ -657,8 +685,13 @@ class RMSprop(_Elementwise):
         self._state_tensor("sumSquare", x)
 
     def _update(self, x, g, sl, shadow):
-        g = g * self.grad_scale
         s = self.state["sumSquare"][sl]
+        if _fused(x, "rmsprop_step"):
+            # one fused pass (k_optim<RmspropRule>) over w, g, the average and the bf16 shadow
+            r = ops.native_ops.rmsprop_step(x, g, s, self._clr, self.decayRate, self.epsilon, self.grad_scale, shadow)
+            if r is not NotImplemented:
+                return
+        g = g.float() * self.grad_scale
         s.mul_(self.decayRate).addcmul_(g, g, value=1 - self.decayRate)
         x.addcdiv_(g, s.sqrt().add_(self.epsilon), value=-self._clr)
         _write_shadow(shadow, x)
@@ -666,6 +699,8 @@ class RMSprop(_Elementwise):
 
 class Ftrl(_Elementwise):
     """FTRL-proximal (``Ftrl.scala:39``)."""
+
+    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
 
     def __init__(self, learningrate=1e-3, learningrate_power=-0.5, initial_accumulator_value=0.1,
                  l1_regularization_strength=0.0, l2_regularization_strength=0.0,
@@ -683,8 +718,14 @@ class Ftrl(_Elementwise):
         self._state_tensor("linear", x)
 
     def _update(self, x, g, sl, shadow):
-        g = g * self.grad_scale
         acc, lin = self.state["accum"][sl], self.state["linear"][sl]
+        if _fused(x, "ftrl_step"):
+            # one fused pass (k_optim<FtrlRule>) over w, g, the accumulator, linear and the bf16 shadow
+            r = ops.native_ops.ftrl_step(x, g, acc, lin, self.learningRate, self.learningRatePower, self.l1, self.l2,
+                                         self.l2Shrinkage, self.grad_scale, shadow)
+            if r is not NotImplemented:
+                return
+        g = g.float() * self.grad_scale
         gs = g + 2 * self.l2Shrinkage * x if self.l2Shrinkage > 0 else g
         new_acc = acc + g * g
         p = -self.learningRatePower

@@ -565,7 +565,7 @@ class DistriOptimizer(BaseOptimizer):
 
     def _grad_for(self, meth, b: _Bucket):
         """The gradient shard ``meth`` reads for bucket ``b``: the bf16 wire shard itself for methods
-        whose fused kernel widens a bf16 gradient on load (SGD, Adagrad), else the fp32 shard
+        whose fused kernel widens a bf16 gradient on load (``reads_bf16_grad``), else the fp32 shard
         (unpacked once per bucket)."""
         if self.grad_wire is None:
             return self.shard_g

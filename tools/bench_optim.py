@@ -1,0 +1,134 @@
+"""A/B of the update phase of RMSprop, Adadelta, Adamax and Ftrl (one GPU, no model, no data).
+
+A flat fp32 arena of ResNet-50's parameter count with a bf16 shadow and one seeded gradient.  For
+each method two arms over arenas of their own, alternating in one process, ``--rounds`` rounds of
+``--iters`` updates each after warm-up:
+
+  (a) torch    the method's torch elementwise form (``bigdl.optim.fused=false``): a chain of
+               launches with full-size temporaries plus the shadow cast
+  (b) fused    the one-pass rule kernel (csrc/optim_rules.hip)
+
+and, as the bandwidth yardstick, one momentum ``ops.sgd_step`` over the same arena: 20 B per
+element (read w, g, v; write w, v) against 20 B for RMSprop and 28 B for the two-state methods, so
+(b)/sgd should sit near 1.0 and 1.4 from bytes alone (the 2 B shadow write is in every arm).
+
+Times are host wall-clock per update around a device synchronise.  Gate: (b) < (a) in every round,
+for every method.
+
+    python tools/bench_optim.py [--out profiles/optim_fused_ab.txt]
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(_ROOT, "bigdl-1_amd"))
+
+RESNET50_PARAMS = 25_557_032
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--n", type=int, default=RESNET50_PARAMS)
+    ap.add_argument("--out", default=os.path.join(_ROOT, "profiles", "optim_fused_ab.txt"))
+    a = ap.parse_args()
+
+    import torch
+    if not torch.cuda.is_available():
+        print("bench_optim needs a GPU", file=sys.stderr)
+        return 2
+    from bigdl import ops
+    from bigdl import optim as O
+    from bigdl.utils import config
+    from bigdl.utils.engine import Engine
+    Engine.init(device="cuda:0")
+    assert ops.native_status()["loaded"], ops.native_status()
+
+    n = a.n
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    grad = torch.randn(n, device="cuda", generator=gen) * 1e-3
+    w0 = torch.randn(n, device="cuda", generator=gen) * 0.05
+    loss = torch.zeros((), device="cuda")
+    makers = {
+        "RMSprop": (lambda: O.RMSprop(learningrate=0.01, learningrate_decay=0.001), "rmsprop_step", 20),
+        "Adadelta": (lambda: O.Adadelta(decayrate=0.9, epsilon=1e-6), "adadelta_step", 28),
+        "Adamax": (lambda: O.Adamax(), "adamax_step", 28),
+        "Ftrl": (lambda: O.Ftrl(learningrate=0.05, l1_regularization_strength=1e-4, l2_regularization_strength=1e-3,
+                                l2_shrinkage_regularization_strength=1e-4), "ftrl_step", 28),
+    }
+
+    def arm(make, fused):
+        meth = make()
+        w = w0.clone()
+        meth.shadow = torch.empty(n, dtype=torch.bfloat16, device="cuda")
+
+        def run(iters):
+            config.set_property("bigdl.optim.fused", fused)
+            for _ in range(iters):
+                meth.optimize(lambda _x: (loss, grad), w)
+        return run
+
+    w_c, buf_c = w0.clone(), torch.zeros(n, device="cuda")
+    sh_c = torch.empty(n, dtype=torch.bfloat16, device="cuda")
+
+    def sgd(iters):
+        for _ in range(iters):
+            ops.sgd_step(w_c, grad, buf_c, 0.1, 0.9, 0.0, 1e-4, False, False, 1.0, sh_c)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f(a.iters)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.iters * 1e3
+
+    lines = [f"Update phase of the elementwise methods: {n} arena elements (ResNet-50), bf16 shadow, "
+             f"{a.iters} updates per round after {a.warmup} warm-up",
+             "ms per update (host wall-clock around a device synchronise), arms alternated in one process",
+             "bytes: B per element of the fused pass / 20 B of the momentum SGD pass",
+             f"{'method':<9} {'round':>5} {'(a) torch':>10} {'(b) fused':>10} {'sgd':>7} {'a/b':>6} {'b/sgd':>6} "
+             f"{'bytes':>6}"]
+    gate = True
+    try:
+        for name, (make, op, nbytes) in makers.items():
+            assert ops.native_has(op), op
+            arms = (("torch", arm(make, False)), ("fused", arm(make, True)), ("sgd", sgd))
+            # warm-up, with a check that arm (b) reaches the kernel and arm (a) does not
+            real, seen = getattr(ops.native_ops, op), []
+            setattr(ops.native_ops, op, lambda *p, **k: seen.append(real(*p, **k)) or seen[-1])
+            try:
+                arms[0][1](a.warmup)
+                assert not seen, f"{op}: the torch arm called the kernel"
+                arms[1][1](a.warmup)
+                assert len(seen) == a.warmup and all(s is not NotImplemented for s in seen), f"{op} refused"
+            finally:
+                setattr(ops.native_ops, op, real)
+            sgd(a.warmup)
+            torch.cuda.synchronize()
+            for r in range(a.rounds):
+                row = {k: timed(f) for k, f in arms}
+                gate = gate and row["fused"] < row["torch"]
+                lines.append(f"{name:<9} {r:>5} {row['torch']:>10.3f} {row['fused']:>10.3f} {row['sgd']:>7.3f} "
+                             f"{row['torch'] / row['fused']:>6.2f} {row['fused'] / row['sgd']:>6.2f} "
+                             f"{nbytes / 20:>6.2f}")
+            del arms
+            torch.cuda.empty_cache()
+    finally:
+        config.clear_property("bigdl.optim.fused")
+    lines.append(f"gate (b) < (a) in every round, for every method: {'PASS' if gate else 'FAIL'}")
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text + "\n")
+    return 0 if gate else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
