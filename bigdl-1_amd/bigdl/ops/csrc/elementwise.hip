@@ -1,7 +1,8 @@
-// Elementwise kernels: dtype casts, ReLU/Threshold fwd+bwd (K8), fused optimizer updates (K22).
+// Elementwise kernels: dtype casts, ReLU/Threshold fwd+bwd (K8), the fused SGD update (K22; every
+// other elementwise method is a rule of k_optim in optim_rules.hip), wire truncation and layout.
 // All are HBM-bound streaming kernels: 16 B per lane per access, grid-stride, grid capped at
 // 2048 blocks of 256 (cdna_hip_programming.md Guideline 11).
-#include "common.h"
+#include "optim_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // casts
@@ -186,20 +187,6 @@ BIGDL_EXPORT int bigdl_threshold_bwd_f32(const void* gy, const void* ref, void* 
 //   d = nesterov ? g' + mom*v : v (or g' when mom == 0) ; w -= lr * (lrs ? lrs*d : d) ;
 //   shadow = bf16(w)
 // ------------------------------------------------------------------------------------------------
-// gradient loads: fp32, or the bf16 reduce-scatter output of the bf16 wire format (read
-// directly — no separate unpack pass over the shard)
-__device__ __forceinline__ float g_at(const float* g, long long e) { return g[e]; }
-__device__ __forceinline__ float g_at(const bf16_t* g, long long e) { return bf2f(g[e]); }
-__device__ __forceinline__ void g_load4(const float* g, long long i, float* o) {
-  float4 G = reinterpret_cast<const float4*>(g)[i];
-  o[0] = G.x; o[1] = G.y; o[2] = G.z; o[3] = G.w;
-}
-__device__ __forceinline__ void g_load4(const bf16_t* g, long long i, float* o) {
-  uint2 G = reinterpret_cast<const uint2*>(g)[i];
-  o[0] = __uint_as_float(G.x << 16); o[1] = __uint_as_float(G.x & 0xffff0000u);
-  o[2] = __uint_as_float(G.y << 16); o[3] = __uint_as_float(G.y & 0xffff0000u);
-}
-
 template <typename GT, bool MOM, bool NEST, bool FIRST, bool SHADOW, bool PERELEM>
 __global__ void k_sgd(float* __restrict__ w, const GT* __restrict__ g, float* __restrict__ buf,
                       bf16_t* __restrict__ shadow, const float* __restrict__ lrs, const float* __restrict__ wds,
@@ -258,11 +245,7 @@ __global__ void k_sgd(float* __restrict__ w, const GT* __restrict__ g, float* __
     }
     reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
     if (MOM) reinterpret_cast<float4*>(buf)[i] = make_float4(bv[0], bv[1], bv[2], bv[3]);
-    if (SHADOW) {
-      uint32_t lo = (uint32_t)f2bf(wv[0]) | ((uint32_t)f2bf(wv[1]) << 16);
-      uint32_t hi = (uint32_t)f2bf(wv[2]) | ((uint32_t)f2bf(wv[3]) << 16);
-      reinterpret_cast<uint2*>(shadow)[i] = make_uint2(lo, hi);
-    }
+    if (SHADOW) store_shadow4(shadow, i, wv);
   }
 }
 
@@ -324,150 +307,6 @@ BIGDL_EXPORT int bigdl_sgd_g16(float* w, const bf16_t* g, float* buf, bf16_t* sh
                                const float* wds, long long n, float lr, float mom, float damp, float wd, int nesterov,
                                int first, float scale, const float* first_dev, hipStream_t s) {
   return sgd_impl<bf16_t>(w, g, buf, shadow, lrs, wds, n, lr, mom, damp, wd, nesterov, first, scale, first_dev, s);
-}
-
-// ------------------------------------------------------------------------------------------------
-// fused Adam (DL/optim/Adam.scala): m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g² ;
-// w -= step_size * m / (sqrt(v) + eps), step_size = lr * sqrt(1-b2^t) / (1-b1^t)
-// ------------------------------------------------------------------------------------------------
-__global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, bf16_t* __restrict__ shadow, long long n4, float step_size, float b1,
-                       float b2, float eps, float wd, float scale, int tail, const float* __restrict__ dev_n,
-                       float lr, float lr_decay) {
-  long long stride = (long long)gridDim.x * blockDim.x;
-  if (dev_n) {
-    // replay-safe form (HIP graphs): the iteration count n lives on the device, so the decayed
-    // rate and the bias corrections are formed here instead of baked in as a host scalar
-    const float n = dev_n[0], t = n + 1.f;
-    step_size = lr / (1.f + n * lr_decay) * sqrtf(1.f - powf(b2, t)) / (1.f - powf(b1, t));
-  }
-  if (blockIdx.x == 0 && threadIdx.x < tail) {
-    const long long e = n4 * 4 + threadIdx.x;
-    const float gg = g[e] * scale + wd * w[e];
-    const float mm = b1 * m[e] + (1.f - b1) * gg, vv = b2 * v[e] + (1.f - b2) * gg * gg;
-    m[e] = mm;
-    v[e] = vv;
-    const float nw = w[e] - step_size * mm / (sqrtf(vv) + eps);
-    w[e] = nw;
-    if (shadow) shadow[e] = f2bf(nw);
-  }
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 W = reinterpret_cast<float4*>(w)[i];
-    float4 G = reinterpret_cast<const float4*>(g)[i];
-    float4 M = reinterpret_cast<float4*>(m)[i];
-    float4 V = reinterpret_cast<float4*>(v)[i];
-    float wv[4] = {W.x, W.y, W.z, W.w}, gv[4] = {G.x, G.y, G.z, G.w};
-    float mv[4] = {M.x, M.y, M.z, M.w}, vv[4] = {V.x, V.y, V.z, V.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float gg = gv[k] * scale + wd * wv[k];
-      mv[k] = b1 * mv[k] + (1.f - b1) * gg;
-      vv[k] = b2 * vv[k] + (1.f - b2) * gg * gg;
-      wv[k] -= step_size * mv[k] / (sqrtf(vv[k]) + eps);
-    }
-    reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    reinterpret_cast<float4*>(m)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
-    reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    if (shadow) {
-      uint32_t lo = (uint32_t)f2bf(wv[0]) | ((uint32_t)f2bf(wv[1]) << 16);
-      uint32_t hi = (uint32_t)f2bf(wv[2]) | ((uint32_t)f2bf(wv[3]) << 16);
-      reinterpret_cast<uint2*>(shadow)[i] = make_uint2(lo, hi);
-    }
-  }
-}
-
-BIGDL_EXPORT int bigdl_adam(float* w, const float* g, float* m, float* v, bf16_t* shadow, long long n,
-                            float step_size, float b1, float b2, float eps, float wd, float scale, hipStream_t s) {
-  if (n <= 0) return 0;
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(k_adam, dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, w, g, m, v, shadow, n4,
-                     step_size, b1, b2, eps, wd, scale, (int)(n & 3), (const float*)nullptr, 0.f, 0.f);
-  BIGDL_CHECK_LAUNCH();
-}
-
-// dev_n: fp32 [1] iteration count before this step (the caller advances it after the launch)
-BIGDL_EXPORT int bigdl_adam_dev(float* w, const float* g, float* m, float* v, bf16_t* shadow, long long n,
-                                const float* dev_n, float lr, float lr_decay, float b1, float b2, float eps, float wd,
-                                float scale, hipStream_t s) {
-  if (n <= 0) return 0;
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(k_adam, dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, w, g, m, v, shadow, n4, 0.f,
-                     b1, b2, eps, wd, scale, (int)(n & 3), dev_n, lr, lr_decay);
-  BIGDL_CHECK_LAUNCH();
-}
-
-// ------------------------------------------------------------------------------------------------
-// fused Adagrad (DL/optim/Adagrad.scala): g' = scale·g + wd·w ; s += g'² ;
-// w -= clr · g' / (sqrt(s) + 1e-10),  clr = lr / (1 + n·lr_decay) — one pass over (w, g, s) plus the
-// optional bf16 shadow, in place of five torch elementwise kernels.  dev_n (nullable): the
-// iteration count n read on the device (replay-safe under HIP-graph capture); else clr is given.
-// G = bf16: the gradient read straight from the DistriOptimizer's bf16 reduce-scatter wire shard
-// (widened on load, as the SGD kernel does) — no fp32 unpack pass per bucket.
-__device__ __forceinline__ float ag_ld(const float* g, long long e) { return g[e]; }
-__device__ __forceinline__ float ag_ld(const bf16_t* g, long long e) { return bf2f(g[e]); }
-__device__ __forceinline__ void ag_ld4(const float* g, long long i, float (&o)[4]) {
-  const float4 G = reinterpret_cast<const float4*>(g)[i];
-  o[0] = G.x; o[1] = G.y; o[2] = G.z; o[3] = G.w;
-}
-__device__ __forceinline__ void ag_ld4(const bf16_t* g, long long i, float (&o)[4]) {
-  const uint2 u = reinterpret_cast<const uint2*>(g)[i];
-  o[0] = __uint_as_float(u.x << 16); o[1] = __uint_as_float(u.x & 0xFFFF0000u);
-  o[2] = __uint_as_float(u.y << 16); o[3] = __uint_as_float(u.y & 0xFFFF0000u);
-}
-
-template <typename G>
-__global__ void k_adagrad(float* __restrict__ w, const G* __restrict__ g, float* __restrict__ sv,
-                          bf16_t* __restrict__ shadow, long long n4, float clr, float wd, float scale, int tail,
-                          const float* __restrict__ dev_n, float lr, float lr_decay) {
-  if (dev_n) clr = lr / (1.f + dev_n[0] * lr_decay);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  if (blockIdx.x == 0 && threadIdx.x < tail) {
-    const long long e = n4 * 4 + threadIdx.x;
-    const float gg = ag_ld(g, e) * scale + wd * w[e];
-    const float ss = sv[e] + gg * gg;
-    sv[e] = ss;
-    const float nw = w[e] - clr * gg / (sqrtf(ss) + 1e-10f);
-    w[e] = nw;
-    if (shadow) shadow[e] = f2bf(nw);
-  }
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 W = reinterpret_cast<float4*>(w)[i];
-    const float4 S = reinterpret_cast<float4*>(sv)[i];
-    float wv[4] = {W.x, W.y, W.z, W.w}, gv[4], sq[4] = {S.x, S.y, S.z, S.w};
-    ag_ld4(g, i, gv);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gg = gv[k] * scale + wd * wv[k];
-      sq[k] += gg * gg;
-      wv[k] -= clr * gg / (sqrtf(sq[k]) + 1e-10f);
-    }
-    reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    reinterpret_cast<float4*>(sv)[i] = make_float4(sq[0], sq[1], sq[2], sq[3]);
-    if (shadow) {
-      const uint32_t lo = (uint32_t)f2bf(wv[0]) | ((uint32_t)f2bf(wv[1]) << 16);
-      const uint32_t hi = (uint32_t)f2bf(wv[2]) | ((uint32_t)f2bf(wv[3]) << 16);
-      reinterpret_cast<uint2*>(shadow)[i] = make_uint2(lo, hi);
-    }
-  }
-}
-
-BIGDL_EXPORT int bigdl_adagrad(float* w, const float* g, float* sv, bf16_t* shadow, long long n, float clr,
-                               const float* dev_n, float lr, float lr_decay, float wd, float scale, hipStream_t s) {
-  if (n <= 0) return 0;
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(k_adagrad<float>, dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, w, g, sv, shadow, n4,
-                     clr, wd, scale, (int)(n & 3), dev_n, lr, lr_decay);
-  BIGDL_CHECK_LAUNCH();
-}
-
-// the same update with a bf16 gradient (8-B aligned: the host checks)
-BIGDL_EXPORT int bigdl_adagrad_g16(float* w, const bf16_t* g, float* sv, bf16_t* shadow, long long n, float clr,
-                                   const float* dev_n, float lr, float lr_decay, float wd, float scale, hipStream_t s) {
-  if (n <= 0) return 0;
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(k_adagrad<bf16_t>, dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, w, g, sv, shadow, n4,
-                     clr, wd, scale, (int)(n & 3), dev_n, lr, lr_decay);
-  BIGDL_CHECK_LAUNCH();
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,20 +14,7 @@
 // sumsq + fold are the store-pass-plus-sum-pass form of a cross-workgroup reduction
 // (cdna_hip_programming.md Guideline 12): no float atomics, every addition in a fixed order, so the
 // sums are bitwise identical from run to run.
-#include "common.h"
-
-__device__ __forceinline__ float lg_at(const float* g, long long e) { return g[e]; }
-__device__ __forceinline__ float lg_at(const bf16_t* g, long long e) { return bf2f(g[e]); }
-__device__ __forceinline__ void lg_load4(const float* g, long long i, float* o) {
-  float4 G = reinterpret_cast<const float4*>(g)[i];
-  o[0] = G.x; o[1] = G.y; o[2] = G.z; o[3] = G.w;
-}
-// the bf16 wire shard, widened on load (8 B per lane)
-__device__ __forceinline__ void lg_load4(const bf16_t* g, long long i, float* o) {
-  uint2 G = reinterpret_cast<const uint2*>(g)[i];
-  o[0] = __uint_as_float(G.x << 16); o[1] = __uint_as_float(G.x & 0xffff0000u);
-  o[2] = __uint_as_float(G.y << 16); o[3] = __uint_as_float(G.y & 0xffff0000u);
-}
+#include "optim_common.h"
 
 // head / aligned body / tail of a chunk: head = elements before the next multiple of 4
 struct Split {
@@ -66,20 +53,20 @@ __global__ void __launch_bounds__(256) k_lars_sumsq(const float* __restrict__ w,
   for (int i = t; i < p.n4; i += 256) {
     const float4 W = reinterpret_cast<const float4*>(w)[p.i4 + i];
     float gv[4];
-    lg_load4(g, p.i4 + i, gv);
+    g_load4(g, p.i4 + i, gv);
     aw[0] = fmaf(W.x, W.x, aw[0]); aw[1] = fmaf(W.y, W.y, aw[1]);
     aw[2] = fmaf(W.z, W.z, aw[2]); aw[3] = fmaf(W.w, W.w, aw[3]);
 #pragma unroll
     for (int k = 0; k < 4; ++k) ag[k] = fmaf(gv[k], gv[k], ag[k]);
   }
   if (t < p.head) {
-    const float wv = w[p.s + t], gg = lg_at(g, p.s + t);
+    const float wv = w[p.s + t], gg = g_at(g, p.s + t);
     aw[1] = fmaf(wv, wv, aw[1]);
     ag[1] = fmaf(gg, gg, ag[1]);
   }
   if (t < p.tail) {
     const long long e = p.s + p.head + 4ll * p.n4 + t;
-    const float wv = w[e], gg = lg_at(g, e);
+    const float wv = w[e], gg = g_at(g, e);
     aw[2] = fmaf(wv, wv, aw[2]);
     ag[2] = fmaf(gg, gg, ag[2]);
   }
@@ -137,7 +124,7 @@ __global__ void __launch_bounds__(256) k_lars_sgd(float* __restrict__ w, const G
     const float4 W = reinterpret_cast<float4*>(w)[j];
     const float4 B = reinterpret_cast<float4*>(v)[j];
     float wv[4] = {W.x, W.y, W.z, W.w}, bv[4] = {B.x, B.y, B.z, B.w}, gv[4];
-    lg_load4(g, j, gv);
+    g_load4(g, j, gv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       bv[k] = mom * bv[k] + rate * (gv[k] * scale + wd * wv[k]);
@@ -145,11 +132,7 @@ __global__ void __launch_bounds__(256) k_lars_sgd(float* __restrict__ w, const G
     }
     reinterpret_cast<float4*>(w)[j] = make_float4(wv[0], wv[1], wv[2], wv[3]);
     reinterpret_cast<float4*>(v)[j] = make_float4(bv[0], bv[1], bv[2], bv[3]);
-    if (SHADOW) {
-      uint32_t lo = (uint32_t)f2bf(wv[0]) | ((uint32_t)f2bf(wv[1]) << 16);
-      uint32_t hi = (uint32_t)f2bf(wv[2]) | ((uint32_t)f2bf(wv[3]) << 16);
-      reinterpret_cast<uint2*>(shadow)[j] = make_uint2(lo, hi);
-    }
+    if (SHADOW) store_shadow4(shadow, j, wv);
   }
   // scalar head (lanes 0..head-1) and tail (lanes 64..64+tail-1, another wave)
   long long e = -1;
@@ -157,7 +140,7 @@ __global__ void __launch_bounds__(256) k_lars_sgd(float* __restrict__ w, const G
   else if (t >= 64 && t - 64 < p.tail) e = p.s + p.head + 4ll * p.n4 + (t - 64);
   if (e >= 0) {
     const float wv = w[e];
-    const float b = mom * v[e] + rate * (lg_at(g, e) * scale + wd * wv);
+    const float b = mom * v[e] + rate * (g_at(g, e) * scale + wd * wv);
     const float nw = wv - b;
     v[e] = b;
     w[e] = nw;

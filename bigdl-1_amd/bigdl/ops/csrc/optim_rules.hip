@@ -1,32 +1,23 @@
-// Fused updates of the elementwise optimisation methods that have no kernel of their own in
-// elementwise.hip: RMSprop, Adadelta, Adamax, Ftrl, and Adam with a bf16 gradient.
+// Fused updates of every elementwise optimisation method but SGD and LARS: Adam, Adagrad, RMSprop,
+// Adadelta, Adamax and Ftrl.
 //
-// ONE streaming kernel (k_optim), templated on an update rule and on the gradient type, with the
-// structure of k_adagrad: grid-stride float4 body, the n & 3 tail on block 0, long long indices,
-// a bf16 gradient (the DistriOptimizer's reduce-scatter wire shard) widened on load, and the
-// optional bf16 shadow written from the new weight as one uint2.  HBM-bound: 16 B per lane per
-// access, grid capped at 2048 blocks of 256 (cdna_hip_programming.md Guideline 11).
+// ONE streaming kernel (k_optim), templated on an update rule and on the gradient type: grid-stride
+// float4 body, the n & 3 tail on block 0, long long indices, a bf16 gradient (the DistriOptimizer's
+// reduce-scatter wire shard) widened on load, and the optional bf16 shadow written from the new
+// weight as one 8-B store.  HBM-bound: 16 B per lane per access, grid capped at 2048 blocks of 256
+// (cdna_hip_programming.md Guideline 11).
 //
 // A rule is a struct of its hyper-parameters (by value in the kernel arguments) with
 //   NS                     number of fp32 state tensors (1 or 2)
+//   prepare()              called once per thread on the kernel's copy before the loop: Adam and
+//                          Adagrad form their step size here from an iteration count on the device
+//                          (the replay-safe form for HIP-graph capture); empty otherwise
 //   step(w, g, a, b)       the per-element update over the weight, the raw gradient and the states
 // Every rule is the torch form of its class in optim/optim_method.py (the CPU path and the
 // oracle), term for term; constants such as 1 - decay are formed on the host in double, as the
 // torch form does.  Plain IEEE division and sqrtf only: Adamax's default eps = 1e-38 is a subnormal
 // fp32 and must survive (no fast-math, no reciprocal approximations).
-#include "common.h"
-
-__device__ __forceinline__ float ag_ld(const float* g, long long e) { return g[e]; }
-__device__ __forceinline__ float ag_ld(const bf16_t* g, long long e) { return bf2f(g[e]); }
-__device__ __forceinline__ void ag_ld4(const float* g, long long i, float (&o)[4]) {
-  const float4 G = reinterpret_cast<const float4*>(g)[i];
-  o[0] = G.x; o[1] = G.y; o[2] = G.z; o[3] = G.w;
-}
-__device__ __forceinline__ void ag_ld4(const bf16_t* g, long long i, float (&o)[4]) {
-  const uint2 u = reinterpret_cast<const uint2*>(g)[i];
-  o[0] = __uint_as_float(u.x << 16); o[1] = __uint_as_float(u.x & 0xFFFF0000u);
-  o[2] = __uint_as_float(u.y << 16); o[3] = __uint_as_float(u.y & 0xFFFF0000u);
-}
+#include "optim_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // rules
@@ -35,6 +26,7 @@ __device__ __forceinline__ void ag_ld4(const bf16_t* g, long long i, float (&o)[
 struct RmspropRule {
   static constexpr int NS = 1;
   float scale, clr, dr, omdr, eps;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void step(float& w, float g, float& s, float&) const {
     const float gg = g * scale;
     s = dr * s + omdr * gg * gg;
@@ -47,6 +39,7 @@ struct RmspropRule {
 struct AdadeltaRule {
   static constexpr int NS = 2;
   float scale, dr, omdr, eps;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void step(float& w, float g, float& v, float& d) const {
     const float gg = g * scale;
     v = dr * v + omdr * gg * gg;
@@ -62,6 +55,7 @@ struct AdadeltaRule {
 struct AdamaxRule {
   static constexpr int NS = 2;
   float scale, stepsz, b1, omb1, b2, eps;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ void step(float& w, float g, float& m, float& u) const {
     const float gg = g * scale;
     m = b1 * m + omb1 * gg;
@@ -78,6 +72,7 @@ template <int PM>
 struct FtrlRule {
   static constexpr int NS = 2;
   float scale, lr, p, l1, two_l2, two_l2s;
+  __device__ __forceinline__ void prepare() {}
   __device__ __forceinline__ float pw(float x) const {
     if (PM == 0) return sqrtf(x);
     if (PM == 1) return 1.f;
@@ -98,15 +93,43 @@ struct FtrlRule {
   }
 };
 
-// Adam with k_adam's arithmetic (elementwise.hip), for the bf16 gradient instance
+// Adam (DL/optim/Adam.scala): g' = scale·g + wd·w ; m = b1·m + (1-b1)·g' ; v = b2·v + (1-b2)·g'² ;
+// w -= step_size·m / (sqrt(v) + eps), step_size = lr·sqrt(1 - b2^t) / (1 - b1^t) from the host, or,
+// with dev_n (fp32 [1], the iteration count n before this step, t = n + 1), formed here from the
+// decayed rate lr / (1 + n·lr_decay) so that a replayed graph bakes in no host scalar.
 struct AdamRule {
   static constexpr int NS = 2;
   float scale, step_size, b1, b2, eps, wd;
+  const float* dev_n;
+  float lr, lr_decay;
+  __device__ __forceinline__ void prepare() {
+    if (dev_n) {
+      const float n = dev_n[0], t = n + 1.f;
+      step_size = lr / (1.f + n * lr_decay) * sqrtf(1.f - powf(b2, t)) / (1.f - powf(b1, t));
+    }
+  }
   __device__ __forceinline__ void step(float& w, float g, float& m, float& v) const {
     const float gg = g * scale + wd * w;
     m = b1 * m + (1.f - b1) * gg;
     v = b2 * v + (1.f - b2) * gg * gg;
     w -= step_size * m / (sqrtf(v) + eps);
+  }
+};
+
+// Adagrad (DL/optim/Adagrad.scala): g' = scale·g + wd·w ; s += g'² ; w -= clr·g' / (sqrt(s) + 1e-10),
+// clr = lr / (1 + n·lr_decay) from the host, or formed here from dev_n as in AdamRule.
+struct AdagradRule {
+  static constexpr int NS = 1;
+  float scale, clr, wd;
+  const float* dev_n;
+  float lr, lr_decay;
+  __device__ __forceinline__ void prepare() {
+    if (dev_n) clr = lr / (1.f + dev_n[0] * lr_decay);
+  }
+  __device__ __forceinline__ void step(float& w, float g, float& s, float&) const {
+    const float gg = g * scale + wd * w;
+    s += gg * gg;
+    w -= clr * gg / (sqrtf(s) + 1e-10f);
   }
 };
 
@@ -118,11 +141,12 @@ template <typename R, typename G>
 __global__ void k_optim(R r, float* __restrict__ w, const G* __restrict__ g, float* __restrict__ s0,
                         float* __restrict__ s1, bf16_t* __restrict__ shadow, long long n4, int tail) {
   const long long stride = (long long)gridDim.x * blockDim.x;
+  r.prepare();
   if (blockIdx.x == 0 && threadIdx.x < tail) {
     const long long e = n4 * 4 + threadIdx.x;
     float nw = w[e], a = s0[e], b = 0.f;
     if (R::NS > 1) b = s1[e];
-    r.step(nw, ag_ld(g, e), a, b);
+    r.step(nw, g_at(g, e), a, b);
     w[e] = nw;
     s0[e] = a;
     if (R::NS > 1) s1[e] = b;
@@ -136,17 +160,13 @@ __global__ void k_optim(R r, float* __restrict__ w, const G* __restrict__ g, flo
       const float4 B = reinterpret_cast<float4*>(s1)[i];
       bv[0] = B.x; bv[1] = B.y; bv[2] = B.z; bv[3] = B.w;
     }
-    ag_ld4(g, i, gv);
+    g_load4(g, i, gv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) r.step(wv[k], gv[k], av[k], bv[k]);
     reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
     reinterpret_cast<float4*>(s0)[i] = make_float4(av[0], av[1], av[2], av[3]);
     if (R::NS > 1) reinterpret_cast<float4*>(s1)[i] = make_float4(bv[0], bv[1], bv[2], bv[3]);
-    if (shadow) {
-      const uint32_t lo = (uint32_t)f2bf(wv[0]) | ((uint32_t)f2bf(wv[1]) << 16);
-      const uint32_t hi = (uint32_t)f2bf(wv[2]) | ((uint32_t)f2bf(wv[3]) << 16);
-      reinterpret_cast<uint2*>(shadow)[i] = make_uint2(lo, hi);
-    }
+    if (shadow) store_shadow4(shadow, i, wv);
   }
 }
 
@@ -213,8 +233,31 @@ BIGDL_EXPORT int bigdl_ftrl_g16(float* w, const bf16_t* g, float* acc, float* li
   return ftrl_launch(w, g, acc, lin, shadow, n, lr, p, l1, two_l2, two_l2s, scale, s);
 }
 
-// bigdl_adam with a bf16 gradient (g 8-B aligned)
+// step_size = lr · sqrt(1 - b2^t) / (1 - b1^t)
+BIGDL_EXPORT int bigdl_adam(float* w, const float* g, float* m, float* v, bf16_t* shadow, long long n,
+                            float step_size, float b1, float b2, float eps, float wd, float scale, hipStream_t s) {
+  return optim_launch(AdamRule{scale, step_size, b1, b2, eps, wd, nullptr, 0.f, 0.f}, w, g, m, v, shadow, n, s);
+}
+
 BIGDL_EXPORT int bigdl_adam_g16(float* w, const bf16_t* g, float* m, float* v, bf16_t* shadow, long long n,
                                 float step_size, float b1, float b2, float eps, float wd, float scale, hipStream_t s) {
-  return optim_launch(AdamRule{scale, step_size, b1, b2, eps, wd}, w, g, m, v, shadow, n, s);
+  return optim_launch(AdamRule{scale, step_size, b1, b2, eps, wd, nullptr, 0.f, 0.f}, w, g, m, v, shadow, n, s);
+}
+
+// dev_n: fp32 [1] iteration count before this step (the caller advances it after the launch)
+BIGDL_EXPORT int bigdl_adam_dev(float* w, const float* g, float* m, float* v, bf16_t* shadow, long long n,
+                                const float* dev_n, float lr, float lr_decay, float b1, float b2, float eps, float wd,
+                                float scale, hipStream_t s) {
+  return optim_launch(AdamRule{scale, 0.f, b1, b2, eps, wd, dev_n, lr, lr_decay}, w, g, m, v, shadow, n, s);
+}
+
+// dev_n nullable: with it the rate is formed on the device and clr is ignored
+BIGDL_EXPORT int bigdl_adagrad(float* w, const float* g, float* sv, bf16_t* shadow, long long n, float clr,
+                               const float* dev_n, float lr, float lr_decay, float wd, float scale, hipStream_t s) {
+  return optim_launch(AdagradRule{scale, clr, wd, dev_n, lr, lr_decay}, w, g, sv, (float*)nullptr, shadow, n, s);
+}
+
+BIGDL_EXPORT int bigdl_adagrad_g16(float* w, const bf16_t* g, float* sv, bf16_t* shadow, long long n, float clr,
+                                   const float* dev_n, float lr, float lr_decay, float wd, float scale, hipStream_t s) {
+  return optim_launch(AdagradRule{scale, clr, wd, dev_n, lr, lr_decay}, w, g, sv, (float*)nullptr, shadow, n, s);
 }

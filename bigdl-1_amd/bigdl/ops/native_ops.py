@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -1843,13 +1844,35 @@ def _wgrad_async_or_inline(x, gy, w4, gw_acc, scale, stride, pad, dilation, pad_
 
 
 # ------------------------------------------------------------------------------------------------ optimizers
-def _vec_ok(*ts, n):
-    for t in ts:
-        if t is None:
-            continue
-        if not (t.is_cuda and t.is_contiguous() and t.numel() == n and _al16(t)):
-            return False
-    return True
+def _rule_ok(w, g, states, shadow, extra=()):
+    """The operand contract of every update kernel (csrc/elementwise.hip k_sgd, optim_rules.hip,
+    lars.hip), in one place, so that a mis-shaped launch never reaches the GPU:
+
+    * ``w`` and every tensor of ``states`` (momentum, averages, per-element rates): fp32, on the
+      device, contiguous, as long as ``w``, 16-B aligned;
+    * ``g``: fp32 (16-B aligned) or bf16 (the wire shard, 8-B aligned), device, contiguous, same length;
+    * ``shadow``: bf16, device, contiguous, same length, 8-B aligned;
+    * ``extra`` (iteration counters and flags the kernel reads): fp32 on the device.
+
+    ``None`` among ``states``, ``extra`` and for ``shadow`` means the operand is not passed."""
+    n = w.numel()
+
+    def vec(t, dtypes, align):
+        return (t.dtype in dtypes and t.is_cuda and t.is_contiguous() and t.numel() == n
+                and t.data_ptr() % align == 0)
+
+    if not all(vec(t, (_f32,), 16) for t in (w, *states) if t is not None):
+        return False
+    if not vec(g, (_f32, _bf16), 8 if g.dtype == _bf16 else 16):
+        return False
+    if shadow is not None and not vec(shadow, (_bf16,), 8):
+        return False
+    return all(t.is_cuda and t.dtype == _f32 for t in extra if t is not None)
+
+
+def _entry(name, g):
+    """The entry point ``name`` of the library, or its ``_g16`` twin when the gradient is bf16."""
+    return getattr(_lib(), name + "_g16" if g.dtype == _bf16 else name)
 
 
 @register("sgd_step")
@@ -1858,23 +1881,12 @@ def sgd_step(w, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_s
     """Fused SGD over a flat fp32 slice; ``g`` is fp32 or bf16 (the bf16-wire reduce-scatter output,
     read directly by the kernel instead of being unpacked into an fp32 shard first)."""
     F3.mark_dirty(w)
-    n = w.numel()
-    if w.dtype != _f32 or g.dtype not in (_f32, _bf16) or not _vec_ok(w, buf, lrs, wds, n=n):
+    if not _rule_ok(w, g, (buf, lrs, wds), shadow, (first_dev,)) or (momentum != 0 and buf is None):
         return NotImplemented
-    g16 = g.dtype == _bf16
-    if not (g.is_cuda and g.is_contiguous() and g.numel() == n and g.data_ptr() % (8 if g16 else 16) == 0):
-        return NotImplemented
-    if shadow is not None and not (shadow.dtype == _bf16 and shadow.is_contiguous() and shadow.numel() == n
-                                   and shadow.data_ptr() % 8 == 0):
-        return NotImplemented
-    if momentum != 0 and buf is None:
-        return NotImplemented
-    if first_dev is not None and not (first_dev.is_cuda and first_dev.dtype == _f32):
-        return NotImplemented
-    fn = _lib().bigdl_sgd_g16 if g16 else _lib().bigdl_sgd
-    check(fn(ptr(w), ptr(g), ptr(buf if momentum != 0 else None), ptr(shadow), ptr(lrs), ptr(wds),
-             _ll(n), _f(lr), _f(momentum), _f(dampening), _f(weight_decay), C.c_int(int(bool(nesterov))),
-             C.c_int(int(bool(first_step))), _f(grad_scale), ptr(first_dev), _s()), "sgd")
+    check(_entry("bigdl_sgd", g)(ptr(w), ptr(g), ptr(buf if momentum != 0 else None), ptr(shadow), ptr(lrs), ptr(wds),
+                                 _ll(w.numel()), _f(lr), _f(momentum), _f(dampening), _f(weight_decay),
+                                 C.c_int(int(bool(nesterov))), C.c_int(int(bool(first_step))), _f(grad_scale),
+                                 ptr(first_dev), _s()), "sgd")
     return w
 
 
@@ -1883,18 +1895,12 @@ def _lars_table_ok(table, w):
             and hasattr(_lib(), "bigdl_lars_sgd"))
 
 
-def _lars_g_ok(g, n):
-    g16 = g.dtype == _bf16
-    return (g.dtype in (_f32, _bf16) and g.is_cuda and g.is_contiguous() and g.numel() == n
-            and g.data_ptr() % (8 if g16 else 16) == 0)
-
-
 @register("lars_sumsq")
 def lars_sumsq(w, g, table, sums=None):
     """Per-layer (Σw², Σg²) of the owned pieces of ``table`` (bigdl_lars_sumsq + bigdl_lars_fold:
     one partial per chunk, then one fixed-order sum per layer; no float atomics).  ``g`` is fp32 or
     the bf16 wire shard.  Returns fp32 ``[2·L]`` (``sums`` when given)."""
-    if not _lars_table_ok(table, w) or w.dtype != _f32 or not _vec_ok(w, n=table.n) or not _lars_g_ok(g, table.n):
+    if not _lars_table_ok(table, w) or not _rule_ok(w, g, (), None):
         return NotImplemented
     if sums is None:
         sums = torch.empty(2 * table.n_layers, dtype=_f32, device=w.device)
@@ -1913,16 +1919,13 @@ def lars_step(w, g, v, table, sums, hyper, grad_scale=1.0, shadow=None, c0=0, c1
     the ``[L, 4]`` hyper-parameter rows are read on the device."""
     F3.mark_dirty(w)
     c1 = getattr(table, "n_chunks", 0) if c1 is None else c1
-    if not _lars_table_ok(table, w) or w.dtype != _f32 or not _vec_ok(w, v, n=table.n) or v.dtype != _f32:
+    if not _lars_table_ok(table, w) or not _rule_ok(w, g, (v,), shadow, (sums, hyper)):
         return NotImplemented
-    if not _lars_g_ok(g, table.n) or not 0 <= c0 <= c1 <= table.n_chunks:
+    if not 0 <= c0 <= c1 <= table.n_chunks:
         return NotImplemented
     for t, m in ((sums, 2 * table.n_layers), (hyper, 4 * table.n_layers)):
-        if not (t.is_cuda and t.dtype == _f32 and t.is_contiguous() and t.numel() == m):
+        if not (t.is_contiguous() and t.numel() == m):
             return NotImplemented
-    if shadow is not None and not (shadow.is_cuda and shadow.dtype == _bf16 and shadow.is_contiguous()
-                                   and shadow.numel() == table.n and shadow.data_ptr() % 8 == 0):
-        return NotImplemented
     check(_lib().bigdl_lars_sgd(ptr(w), ptr(g), C.c_int(int(g.dtype == _bf16)), ptr(v), ptr(shadow), ptr(table.cstart),
                                 ptr(table.clen), ptr(table.clayer), ptr(sums), ptr(hyper), C.c_int(c0), C.c_int(c1),
                                 _f(grad_scale), _s()), "lars_sgd")
@@ -1931,84 +1934,43 @@ def lars_step(w, g, v, table, sums, hyper, grad_scale=1.0, shadow=None, c0=0, c1
 
 @register("adam_step")
 def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None):
-    """Fused Adam; ``g`` is fp32 or bf16 (the bf16 wire shard, widened on load: bigdl_adam_g16)."""
-    import math
+    """Fused Adam (bigdl_adam); ``step`` is the 1-based iteration, the bias-corrected step size is
+    formed here.  ``g`` is fp32 or bf16 (the bf16 wire shard, widened on load)."""
     F3.mark_dirty(w)
-    n = w.numel()
-    if g.dtype == _bf16:
-        if not _rule_ok(w, g, (m, v), shadow):
-            return NotImplemented
-        fn = _lib().bigdl_adam_g16
-    else:
-        if w.dtype != _f32 or g.dtype != _f32 or not _vec_ok(w, g, m, v, n=n):
-            return NotImplemented
-        if shadow is not None and not (shadow.dtype == _bf16 and shadow.is_contiguous() and shadow.numel() == n
-                                       and shadow.data_ptr() % 8 == 0):
-            return NotImplemented
-        fn = _lib().bigdl_adam
+    if not _rule_ok(w, g, (m, v), shadow):
+        return NotImplemented
     step_size = lr * math.sqrt(1 - beta2 ** step) / (1 - beta1 ** step)
-    check(fn(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(n), _f(step_size), _f(beta1), _f(beta2),
-             _f(eps), _f(weight_decay), _f(grad_scale), _s()), "adam")
+    check(_entry("bigdl_adam", g)(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(w.numel()), _f(step_size),
+                                  _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _f(grad_scale), _s()), "adam")
     return w
 
 
 @register("adam_step_dev")
 def adam_step_dev(w, g, m, v, dev_n, lr, lr_decay, beta1, beta2, eps, weight_decay=0.0, grad_scale=1.0, shadow=None):
     """Adam whose iteration count ``dev_n`` (fp32 [1], before this step) is read on the device —
-    the replay-safe form for HIP-graph capture; the caller advances ``dev_n`` afterwards."""
+    the replay-safe form for HIP-graph capture; the caller advances ``dev_n`` afterwards.  fp32
+    gradient only."""
     F3.mark_dirty(w)
-    n = w.numel()
-    if w.dtype != _f32 or g.dtype != _f32 or not _vec_ok(w, g, m, v, n=n) or not (dev_n.is_cuda and
-                                                                                  dev_n.dtype == _f32):
+    if g.dtype != _f32 or dev_n is None or not _rule_ok(w, g, (m, v), shadow, (dev_n,)):
         return NotImplemented
-    if shadow is not None and not (shadow.dtype == _bf16 and shadow.is_contiguous() and shadow.numel() == n
-                                   and shadow.data_ptr() % 8 == 0):
-        return NotImplemented
-    check(_lib().bigdl_adam_dev(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(n), ptr(dev_n), _f(lr), _f(lr_decay),
-                                _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _f(grad_scale), _s()), "adam_dev")
+    check(_lib().bigdl_adam_dev(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(w.numel()), ptr(dev_n), _f(lr),
+                                _f(lr_decay), _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _f(grad_scale), _s()),
+          "adam_dev")
     return w
 
 
 @register("adagrad_step")
 def adagrad_step(w, g, s, lr, lr_decay, n, weight_decay=0.0, grad_scale=1.0, shadow=None, dev_n=None):
     """Fused Adagrad update (bigdl_adagrad); ``dev_n`` (fp32 [1] on the device, the iteration count
-    before this step) makes it replay-safe under HIP-graph capture, else ``n`` (host) is used."""
+    before this step) makes it replay-safe under HIP-graph capture, else ``n`` (host) is used.
+    ``g`` is fp32 or the bf16 wire shard."""
     F3.mark_dirty(w)
-    numel = w.numel()
-    g16 = g.dtype == _bf16  # the DistriOptimizer's bf16 wire shard, widened on load
-    if w.dtype != _f32 or s.dtype != _f32 or not _vec_ok(w, s, n=numel):
+    if not _rule_ok(w, g, (s,), shadow, (dev_n,)):
         return NotImplemented
-    if g16:
-        if not (g.is_cuda and g.is_contiguous() and g.numel() == numel and g.data_ptr() % 8 == 0):
-            return NotImplemented
-    elif g.dtype != _f32 or not _vec_ok(g, n=numel):
-        return NotImplemented
-    if dev_n is not None and not (dev_n.is_cuda and dev_n.dtype == _f32):
-        return NotImplemented
-    if shadow is not None and not (shadow.dtype == _bf16 and shadow.is_contiguous() and shadow.numel() == numel
-                                   and shadow.data_ptr() % 8 == 0):
-        return NotImplemented
-    clr = lr / (1 + n * lr_decay)
-    fn = _lib().bigdl_adagrad_g16 if g16 else _lib().bigdl_adagrad
-    check(fn(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(numel), _f(clr), ptr(dev_n), _f(lr), _f(lr_decay),
-             _f(weight_decay), _f(grad_scale), _s()), "adagrad")
+    check(_entry("bigdl_adagrad", g)(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(w.numel()), _f(lr / (1 + n * lr_decay)),
+                                     ptr(dev_n), _f(lr), _f(lr_decay), _f(weight_decay), _f(grad_scale), _s()),
+          "adagrad")
     return w
-
-
-def _rule_ok(w, g, states, shadow):
-    """Operand contract of the rule kernels (csrc/optim_rules.hip): ``w`` and the states fp32, device,
-    contiguous, equally long, 16-B aligned; ``g`` fp32 (16-B aligned) or bf16 (8-B aligned);
-    ``shadow`` None or bf16, contiguous, 8-B aligned."""
-    n = w.numel()
-    if w.dtype != _f32 or any(s.dtype != _f32 for s in states) or not _vec_ok(w, *states, n=n):
-        return False
-    if g.dtype == _bf16:
-        if not (g.is_cuda and g.is_contiguous() and g.numel() == n and g.data_ptr() % 8 == 0):
-            return False
-    elif g.dtype != _f32 or not _vec_ok(g, n=n):
-        return False
-    return shadow is None or (shadow.is_cuda and shadow.dtype == _bf16 and shadow.is_contiguous()
-                              and shadow.numel() == n and shadow.data_ptr() % 8 == 0)
 
 
 @register("rmsprop_step")
@@ -2018,7 +1980,7 @@ def rmsprop_step(w, g, s, clr, decay_rate, eps, grad_scale=1.0, shadow=None):
     F3.mark_dirty(w)
     if not _rule_ok(w, g, (s,), shadow):
         return NotImplemented
-    fn = _lib().bigdl_rmsprop_g16 if g.dtype == _bf16 else _lib().bigdl_rmsprop
+    fn = _entry("bigdl_rmsprop", g)
     check(fn(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(w.numel()), _f(clr), _f(decay_rate), _f(1 - decay_rate),
              _f(eps), _f(grad_scale), _s()), "rmsprop")
     return w
@@ -2031,7 +1993,7 @@ def adadelta_step(w, g, v, d, decay_rate, eps, grad_scale=1.0, shadow=None):
     F3.mark_dirty(w)
     if not _rule_ok(w, g, (v, d), shadow):
         return NotImplemented
-    fn = _lib().bigdl_adadelta_g16 if g.dtype == _bf16 else _lib().bigdl_adadelta
+    fn = _entry("bigdl_adadelta", g)
     check(fn(ptr(w), ptr(g), ptr(v), ptr(d), ptr(shadow), _ll(w.numel()), _f(decay_rate), _f(1 - decay_rate),
              _f(eps), _f(grad_scale), _s()), "adadelta")
     return w
@@ -2044,7 +2006,7 @@ def adamax_step(w, g, m, u, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=
     F3.mark_dirty(w)
     if not _rule_ok(w, g, (m, u), shadow):
         return NotImplemented
-    fn = _lib().bigdl_adamax_g16 if g.dtype == _bf16 else _lib().bigdl_adamax
+    fn = _entry("bigdl_adamax", g)
     check(fn(ptr(w), ptr(g), ptr(m), ptr(u), ptr(shadow), _ll(w.numel()), _f(lr / (1 - beta1 ** step)), _f(beta1),
              _f(1 - beta1), _f(beta2), _f(eps), _f(grad_scale), _s()), "adamax")
     return w
@@ -2057,7 +2019,7 @@ def ftrl_step(w, g, accum, linear, lr, lr_power, l1, l2, l2_shrinkage, grad_scal
     F3.mark_dirty(w)
     if not _rule_ok(w, g, (accum, linear), shadow):
         return NotImplemented
-    fn = _lib().bigdl_ftrl_g16 if g.dtype == _bf16 else _lib().bigdl_ftrl
+    fn = _entry("bigdl_ftrl", g)
     check(fn(ptr(w), ptr(g), ptr(accum), ptr(linear), ptr(shadow), _ll(w.numel()), _f(lr), _f(-lr_power), _f(l1),
              _f(2 * l2), _f(2 * l2_shrinkage), _f(grad_scale), _s()), "ftrl")
     return w

@@ -5,12 +5,13 @@ Interface kept: ``optimize(feval, x) -> (x, [fx])`` where ``feval(x) -> (loss, g
 are attributes (``loadFromTable`` / ``getHyperParameter`` / ``updateHyperParameter``).
 
 Device path: ``x``/``grad`` are flat fp32 arenas (or this rank's shard of one); the whole update is
-ONE fused HIP kernel over the flat buffer (``ops.sgd_step`` / ``ops.adam_step``, K22) that also
-folds in the 1/N gradient averaging (``grad_scale``) and writes the bf16 shadow copy used by the
-next forward.  Adagrad, and — under ``bigdl.optim.fused`` — Adamax, Adadelta, RMSprop and Ftrl
-update the same way (``ops/csrc/optim_rules.hip``); their torch forms below stay the CPU path and
-the kernels' oracle.  ``SGD``'s learning rate follows the reference's negative ``clr`` convention
-(``SGD.scala:61-124``): schedules produce ``currentRate = -lr``.
+ONE fused HIP kernel over the flat buffer (K22) that also folds in the 1/N gradient averaging
+(``grad_scale``) and writes the bf16 shadow copy used by the next forward: ``k_sgd`` for SGD, and
+one rule of ``k_optim`` (``ops/csrc/optim_rules.hip``) for every :class:`_Elementwise` method —
+Adam, Adagrad and, under ``bigdl.optim.fused``, Adamax, Adadelta, RMSprop and Ftrl; their torch
+forms below stay the CPU path and the kernels' oracle.  ``SGD``'s learning rate follows the
+reference's negative ``clr`` convention (``SGD.scala:61-124``): schedules produce
+``currentRate = -lr``.
 """
 from __future__ import annotations
 
@@ -447,9 +448,69 @@ class SGD(OptimMethod):
 
 
 # ----------------------------------------------------------------------------------------- Adam family
-class Adam(OptimMethod):
+def _write_shadow(shadow, x):
+    if shadow is not None:
+        if ops.cast_copy(shadow, x) is NotImplemented:
+            shadow.copy_(x)
+
+
+def _kernel(x, op, gated=True):
+    """True when the update of ``x`` goes to the one-pass rule kernel ``op`` (csrc/optim_rules.hip):
+    device weights, the kernel loaded and, for the methods it gates, ``bigdl.optim.fused`` on."""
+    return x.is_cuda and ops.native_has(op) and bool(not gated or config.get_property("bigdl.optim.fused"))
+
+
+class _Elementwise(OptimMethod):
+    """An update that is elementwise in (x, g, state): ``begin_iteration`` advances the per-iteration
+    scalars and sizes the state like ``x``; ``apply_update`` runs the update on ``[lo, hi)`` — so the
+    DistriOptimizer can run it on this rank's shard only, bucket by bucket (the reference runs every
+    OptimMethod on its partition ``[paramLocalStart, +paramLocalLen)``,
+    ``DL/optim/DistriOptimizer.scala:378-386``).  ``optimize`` (local) is the same two calls over
+    the whole buffer, so the sharded and local updates are one implementation.
+
+    A method gives ``_begin``, ``_native`` (one fused pass of ``k_optim<its rule>`` over x, g, the
+    state and the bf16 shadow) and ``_torch`` (the CPU path and the kernel's oracle); ``_update`` is
+    the only place that chooses between them."""
+
+    supports_slices = True
     reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
 
+    def _begin(self, x):  # per-iteration scalars + state tensors shaped like x
+        raise NotImplementedError
+
+    def _native(self, x, g, sl, shadow):  # x, g: the [lo, hi) slices, g raw; sl: slice object for state
+        return NotImplemented             # NotImplemented = not taken, nothing touched
+
+    def _torch(self, x, g, sl):  # g = g.float() * grad_scale
+        raise NotImplementedError
+
+    def _update(self, x, g, sl, shadow):
+        if self._native(x, g, sl, shadow) is NotImplemented:
+            self._torch(x, g.float() * self.grad_scale, sl)
+            _write_shadow(shadow, x)
+
+    def begin_iteration(self, x):
+        self._begin(x)
+        self.state["evalCounter"] = self.state.get("evalCounter", 0) + 1
+
+    def apply_update(self, x, g, lo, hi, shadow=None):
+        self._update(x[lo:hi], g[lo:hi], slice(lo, hi), shadow)
+
+    def optimize(self, feval, x):
+        fx, g = feval(x)
+        self.begin_iteration(x)
+        self._update(x, g, slice(0, x.numel()), self.shadow)
+        return x, [fx]
+
+    def _device_counter(self, x):
+        """The iteration count as an fp32 device scalar (graph mode: a replay bakes in no host value)."""
+        nt = self.state.get("_dev_n")
+        if not isinstance(nt, torch.Tensor) or nt.device != x.device:
+            nt = self.state["_dev_n"] = torch.full((1,), float(self.state.get("evalCounter", 0)), device=x.device)
+        return nt
+
+
+class Adam(_Elementwise):
     def __init__(self, learningrate=1e-3, learningrate_decay=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8,
                  bigdl_type="float"):
         super().__init__()
@@ -460,42 +521,31 @@ class Adam(OptimMethod):
         n = self.state.get("evalCounter", 0)
         return self.learningRate / (1 + n * self.learningRateDecay)
 
-    supports_slices = True
-
-    def begin_iteration(self, x):
+    def _begin(self, x):
         n = self.state.get("evalCounter", 0)
         self._clr = self.learningRate / (1 + n * self.learningRateDecay)
         self._t = n + 1
         self._state_tensor("s", x)
         self._state_tensor("r", x)
-        self.state["evalCounter"] = self._t
 
-    def apply_update(self, x, g, lo, hi, shadow=None):
-        ops.adam_step(x[lo:hi], g[lo:hi], self.state["s"][lo:hi], self.state["r"][lo:hi], self._clr, self.beta1,
-                      self.beta2, self.epsilon, self._t, 0.0, self.grad_scale, shadow)
+    def _native(self, x, g, sl, shadow):
+        # the dispatcher takes every operand: the kernel on the device, reference.adam_step (the
+        # torch form, shadow included) on the CPU or when the kernel refuses
+        return ops.adam_step(x, g, self.state["s"][sl], self.state["r"][sl], self._clr, self.beta1, self.beta2,
+                             self.epsilon, self._t, 0.0, self.grad_scale, shadow)
 
     def optimize(self, feval, x):
+        if not (getattr(self, "_graph_mode", False) and x.is_cuda):
+            return super().optimize(feval, x)
+        # replay-safe: iteration count on the device, decayed rate / bias corrections in the kernel
         fx, g = feval(x)
-        n = self.state.get("evalCounter", 0)
-        clr = self.learningRate / (1 + n * self.learningRateDecay)
-        t = n + 1
-        m = self._state_tensor("s", x)
-        v = self._state_tensor("r", x)
-        if getattr(self, "_graph_mode", False) and x.is_cuda:
-            # replay-safe: iteration count on the device, decayed rate / bias corrections in the kernel
-            nt = self.state.get("_dev_n")
-            if not isinstance(nt, torch.Tensor) or nt.device != x.device:
-                nt = torch.full((1,), float(n), device=x.device)
-                self.state["_dev_n"] = nt
-            r = ops.native_ops.adam_step_dev(x, g, m, v, nt, self.learningRate, self.learningRateDecay, self.beta1,
-                                             self.beta2, self.epsilon, 0.0, self.grad_scale, self.shadow)
-            if r is NotImplemented:
-                raise NotImplementedError("Adam graph mode needs the native fused kernel")
-            nt.add_(1)
-        else:
-            ops.adam_step(x, g, m, v, clr, self.beta1, self.beta2, self.epsilon, t, 0.0, self.grad_scale,
-                          self.shadow)
-        self.state["evalCounter"] = t
+        m, v, nt = self._state_tensor("s", x), self._state_tensor("r", x), self._device_counter(x)
+        r = ops.native_ops.adam_step_dev(x, g, m, v, nt, self.learningRate, self.learningRateDecay, self.beta1,
+                                         self.beta2, self.epsilon, 0.0, self.grad_scale, self.shadow)
+        if r is NotImplemented:
+            raise NotImplementedError("Adam graph mode needs the native fused kernel")
+        nt.add_(1)
+        self.state["evalCounter"] = self.state.get("evalCounter", 0) + 1
         return x, [fx]
 
     def prepare_graph(self) -> bool:
@@ -514,51 +564,7 @@ class ParallelAdam(Adam):
         super().__init__(learningrate, learningrate_decay, beta1, beta2, epsilon)
 
 
-class _Elementwise(OptimMethod):
-    """An update that is elementwise in (x, g, state): ``begin_iteration`` advances the per-iteration
-    scalars and sizes the state like ``x``; ``apply_update`` runs the update on ``[lo, hi)`` — so the
-    DistriOptimizer can run it on this rank's shard only, bucket by bucket (the reference runs every
-    OptimMethod on its partition ``[paramLocalStart, +paramLocalLen)``,
-    ``DL/optim/DistriOptimizer.scala:378-386``).  ``optimize`` (local) is the same two calls over
-    the whole buffer, so the sharded and local updates are one implementation."""
-
-    supports_slices = True
-
-    def _begin(self, x):  # per-iteration scalars + state tensors shaped like x
-        raise NotImplementedError
-
-    def _update(self, x, g, sl, shadow):  # x, g: the [lo, hi) slices; sl: slice object for state
-        raise NotImplementedError
-
-    def begin_iteration(self, x):
-        self._begin(x)
-        self.state["evalCounter"] = self.state.get("evalCounter", 0) + 1
-
-    def apply_update(self, x, g, lo, hi, shadow=None):
-        self._update(x[lo:hi], g[lo:hi], slice(lo, hi), shadow)
-
-    def optimize(self, feval, x):
-        fx, g = feval(x)
-        self.begin_iteration(x)
-        self._update(x, g, slice(0, x.numel()), self.shadow)
-        return x, [fx]
-
-
-def _write_shadow(shadow, x):
-    if shadow is not None:
-        if ops.cast_copy(shadow, x) is NotImplemented:
-            shadow.copy_(x)
-
-
-def _fused(x, op):
-    """True when the update of ``x`` goes to the one-pass rule kernel ``op`` (csrc/optim_rules.hip):
-    device weights, ``bigdl.optim.fused`` on and the kernel loaded."""
-    return x.is_cuda and config.get_property("bigdl.optim.fused") and ops.native_has(op)
-
-
 class Adamax(_Elementwise):
-    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
-
     def __init__(self, learningrate=0.002, beta1=0.9, beta2=0.999, epsilon=1e-38, bigdl_type="float"):
         super().__init__()
         self.learningRate, self.beta1, self.beta2, self.epsilon = learningrate, beta1, beta2, epsilon
@@ -568,19 +574,17 @@ class Adamax(_Elementwise):
         self._state_tensor("m", x)
         self._state_tensor("u", x)
 
-    def _update(self, x, g, sl, shadow):
+    def _native(self, x, g, sl, shadow):
+        if not _kernel(x, "adamax_step"):
+            return NotImplemented
+        return ops.native_ops.adamax_step(x, g, self.state["m"][sl], self.state["u"][sl], self.learningRate,
+                                          self.beta1, self.beta2, self.epsilon, self._t, self.grad_scale, shadow)
+
+    def _torch(self, x, g, sl):
         m, u = self.state["m"][sl], self.state["u"][sl]
-        if _fused(x, "adamax_step"):
-            # one fused pass (k_optim<AdamaxRule>) over w, g, m, u and the bf16 shadow
-            r = ops.native_ops.adamax_step(x, g, m, u, self.learningRate, self.beta1, self.beta2, self.epsilon,
-                                           self._t, self.grad_scale, shadow)
-            if r is not NotImplemented:
-                return
-        g = g.float() * self.grad_scale
         m.mul_(self.beta1).add_(g, alpha=1 - self.beta1)
         torch.maximum(u * self.beta2, g.abs() + self.epsilon, out=u)
         x.addcdiv_(m, u, value=-self.learningRate / (1 - self.beta1 ** self._t))
-        _write_shadow(shadow, x)
 
 
 class Adagrad(_Elementwise):
@@ -592,52 +596,37 @@ class Adagrad(_Elementwise):
         self._n = self.state.get("evalCounter", 0)
         self._state_tensor("paramVariance", x)
 
-    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
+    def _native(self, x, g, sl, shadow, dev_n=None):
+        if not _kernel(x, "adagrad_step", gated=False):
+            return NotImplemented
+        return ops.native_ops.adagrad_step(x, g, self.state["paramVariance"][sl], self.learningRate,
+                                           self.learningRateDecay, self._n, self.weightDecay, self.grad_scale, shadow,
+                                           dev_n=dev_n)
 
-    def _update(self, x, g, sl, shadow):
-        n = self._n
+    def _torch(self, x, g, sl, dev_n=None):
         s = self.state["paramVariance"][sl]
-        if x.is_cuda and ops.native_has("adagrad_step"):
-            # one fused pass (k_adagrad) over w, g, the accumulator and the bf16 shadow
-            r = ops.native_ops.adagrad_step(x, g, s, self.learningRate, self.learningRateDecay, n, self.weightDecay,
-                                            self.grad_scale, shadow)
-            if r is not NotImplemented:
-                return
-        g = g.float() * self.grad_scale
         if self.weightDecay != 0:
             g = g + self.weightDecay * x
         s.addcmul_(g, g)
-        clr = self.learningRate / (1 + n * self.learningRateDecay)
-        x.addcdiv_(g, s.sqrt().add_(1e-10), value=-clr)
-        _write_shadow(shadow, x)
+        if dev_n is None:
+            x.addcdiv_(g, s.sqrt().add_(1e-10), value=-self.learningRate / (1 + self._n * self.learningRateDecay))
+        else:  # the decayed rate as a device tensor
+            clr_t = (1 + dev_n * self.learningRateDecay).reciprocal_().mul_(self.learningRate)
+            x.sub_(g / s.sqrt().add_(1e-10) * clr_t)
 
     def optimize(self, feval, x):
         if not getattr(self, "_graph_mode", False):
             return super().optimize(feval, x)
+        # replay-safe: the iteration counter lives on the device, the kernel (or the torch form)
+        # forms the decayed rate from it
         fx, g = feval(x)
-        n = self.state.get("evalCounter", 0)
-        s = self._state_tensor("paramVariance", x)
-        # replay-safe: the iteration counter lives on the device and the decayed rate is a tensor
-        nt = self.state.get("_dev_n")
-        if not isinstance(nt, torch.Tensor) or nt.device != x.device:
-            nt = torch.full((1,), float(n), device=x.device)
-            self.state["_dev_n"] = nt
-        if x.is_cuda and ops.native_has("adagrad_step"):
-            r = ops.native_ops.adagrad_step(x, g, s, self.learningRate, self.learningRateDecay, n, self.weightDecay,
-                                            self.grad_scale, self.shadow, dev_n=nt)
-            if r is not NotImplemented:
-                nt.add_(1)
-                self.state["evalCounter"] = n + 1
-                return x, [fx]
-        g = g * self.grad_scale
-        if self.weightDecay != 0:
-            g = g + self.weightDecay * x
-        s.addcmul_(g, g)
-        clr_t = (1 + nt * self.learningRateDecay).reciprocal_().mul_(self.learningRate)
-        x.sub_(g / s.sqrt().add_(1e-10) * clr_t)
+        self._begin(x)
+        nt, sl = self._device_counter(x), slice(0, x.numel())
+        if self._native(x, g, sl, self.shadow, dev_n=nt) is NotImplemented:
+            self._torch(x, g.float() * self.grad_scale, sl, dev_n=nt)
+            _write_shadow(self.shadow, x)
         nt.add_(1)
-        self.state["evalCounter"] = n + 1
-        _sync_shadow(self, x)
+        self.state["evalCounter"] = self._n + 1
         return x, [fx]
 
     def prepare_graph(self) -> bool:
@@ -646,8 +635,6 @@ class Adagrad(_Elementwise):
 
 
 class Adadelta(_Elementwise):
-    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
-
     def __init__(self, decayrate=0.9, epsilon=1e-10, bigdl_type="float"):
         super().__init__()
         self.decayRate, self.epsilon = decayrate, epsilon
@@ -656,24 +643,21 @@ class Adadelta(_Elementwise):
         self._state_tensor("paramVariance", x)
         self._state_tensor("delta", x)
 
-    def _update(self, x, g, sl, shadow):
+    def _native(self, x, g, sl, shadow):
+        if not _kernel(x, "adadelta_step"):
+            return NotImplemented
+        return ops.native_ops.adadelta_step(x, g, self.state["paramVariance"][sl], self.state["delta"][sl],
+                                            self.decayRate, self.epsilon, self.grad_scale, shadow)
+
+    def _torch(self, x, g, sl):
         v, d = self.state["paramVariance"][sl], self.state["delta"][sl]
-        if _fused(x, "adadelta_step"):
-            # one fused pass (k_optim<AdadeltaRule>) over w, g, both averages and the bf16 shadow
-            r = ops.native_ops.adadelta_step(x, g, v, d, self.decayRate, self.epsilon, self.grad_scale, shadow)
-            if r is not NotImplemented:
-                return
-        g = g.float() * self.grad_scale
         v.mul_(self.decayRate).addcmul_(g, g, value=1 - self.decayRate)
         upd = (d + self.epsilon).sqrt() / (v + self.epsilon).sqrt() * g
         d.mul_(self.decayRate).addcmul_(upd, upd, value=1 - self.decayRate)
         x.sub_(upd)
-        _write_shadow(shadow, x)
 
 
 class RMSprop(_Elementwise):
-    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
-
     def __init__(self, learningrate=1e-2, learningrate_decay=0.0, decayrate=0.99, epsilon=1e-8, bigdl_type="float"):
         super().__init__()
         self.learningRate, self.learningRateDecay = learningrate, learningrate_decay
@@ -684,23 +668,20 @@ class RMSprop(_Elementwise):
         self._clr = self.learningRate / (1 + n * self.learningRateDecay)
         self._state_tensor("sumSquare", x)
 
-    def _update(self, x, g, sl, shadow):
+    def _native(self, x, g, sl, shadow):
+        if not _kernel(x, "rmsprop_step"):
+            return NotImplemented
+        return ops.native_ops.rmsprop_step(x, g, self.state["sumSquare"][sl], self._clr, self.decayRate, self.epsilon,
+                                           self.grad_scale, shadow)
+
+    def _torch(self, x, g, sl):
         s = self.state["sumSquare"][sl]
-        if _fused(x, "rmsprop_step"):
-            # one fused pass (k_optim<RmspropRule>) over w, g, the average and the bf16 shadow
-            r = ops.native_ops.rmsprop_step(x, g, s, self._clr, self.decayRate, self.epsilon, self.grad_scale, shadow)
-            if r is not NotImplemented:
-                return
-        g = g.float() * self.grad_scale
         s.mul_(self.decayRate).addcmul_(g, g, value=1 - self.decayRate)
         x.addcdiv_(g, s.sqrt().add_(self.epsilon), value=-self._clr)
-        _write_shadow(shadow, x)
 
 
 class Ftrl(_Elementwise):
     """FTRL-proximal (``Ftrl.scala:39``)."""
-
-    reads_bf16_grad = True  # apply_update takes the bf16 wire gradient shard (widened in the kernel)
 
     def __init__(self, learningrate=1e-3, learningrate_power=-0.5, initial_accumulator_value=0.1,
                  l1_regularization_strength=0.0, l2_regularization_strength=0.0,
@@ -717,15 +698,15 @@ class Ftrl(_Elementwise):
             self.state["accum"] = torch.full_like(x, self.initialAccumulatorValue, dtype=torch.float32)
         self._state_tensor("linear", x)
 
-    def _update(self, x, g, sl, shadow):
+    def _native(self, x, g, sl, shadow):
+        if not _kernel(x, "ftrl_step"):
+            return NotImplemented
+        return ops.native_ops.ftrl_step(x, g, self.state["accum"][sl], self.state["linear"][sl], self.learningRate,
+                                        self.learningRatePower, self.l1, self.l2, self.l2Shrinkage, self.grad_scale,
+                                        shadow)
+
+    def _torch(self, x, g, sl):
         acc, lin = self.state["accum"][sl], self.state["linear"][sl]
-        if _fused(x, "ftrl_step"):
-            # one fused pass (k_optim<FtrlRule>) over w, g, the accumulator, linear and the bf16 shadow
-            r = ops.native_ops.ftrl_step(x, g, acc, lin, self.learningRate, self.learningRatePower, self.l1, self.l2,
-                                         self.l2Shrinkage, self.grad_scale, shadow)
-            if r is not NotImplemented:
-                return
-        g = g.float() * self.grad_scale
         gs = g + 2 * self.l2Shrinkage * x if self.l2Shrinkage > 0 else g
         new_acc = acc + g * g
         p = -self.learningRatePower
@@ -735,7 +716,6 @@ class Ftrl(_Elementwise):
         l1r = torch.clamp(lin.abs() - self.l1, min=0) * torch.sign(lin)
         x.copy_(torch.where(lin.abs() > self.l1, -l1r / quad, torch.zeros_like(x)))
         acc.copy_(new_acc)
-        _write_shadow(shadow, x)
 
 
 class LBFGS(OptimMethod):

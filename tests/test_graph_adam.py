@@ -1,6 +1,7 @@
 """Adam inside a captured HIP-graph training step: the iteration count lives on the device
-(``bigdl_adam_dev``), so replays follow the eager trajectory (bias corrections and the decayed
-learning rate advance every replay instead of being baked in at capture)."""
+(``bigdl_adam_dev``: ``AdamRule::prepare`` of k_optim forms the step size from it), so replays
+follow the eager trajectory (bias corrections and the decayed learning rate advance every replay
+instead of being baked in at capture)."""
 import copy
 
 import pytest

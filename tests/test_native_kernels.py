@@ -184,9 +184,9 @@ def test_adam():
 
 @pytest.mark.parametrize("graph_counter", [False, True])
 def test_adagrad_fused_matches_optim_method(graph_counter):
-    """k_adagrad (one pass over w, g, the accumulator and the bf16 shadow) against the torch form
-    of Adagrad.optimize (DL/optim/Adagrad.scala), with weight decay and a gradient scale, host or
-    device iteration counter."""
+    """k_optim<AdagradRule> (one pass over w, g, the accumulator and the bf16 shadow) against the
+    torch form of Adagrad.optimize (DL/optim/Adagrad.scala), with weight decay and a gradient scale,
+    host or device iteration counter."""
     N = _native()
     n = 1003  # a tail past the float4 body
     w = torch.randn(n, device=dev)

@@ -1,5 +1,5 @@
-"""The one-pass update kernels of RMSprop, Adadelta, Adamax, Ftrl and bf16-gradient Adam
-(csrc/optim_rules.hip) against the torch forms they replace on the GPU.
+"""The one-pass update kernels of Adam, Adagrad, RMSprop, Adadelta, Adamax and Ftrl (the rules of
+k_optim in csrc/optim_rules.hip) against the torch forms they replace on the GPU.
 
 Kernel numerics are judged three ways from the same fp32 inputs: an fp64 oracle of the formula, the
 fp32 torch form, and the kernel.  With E_t = max|torch_fp32 - oracle| per tensor, the kernel must
@@ -8,13 +8,15 @@ stay within 4·E_t + 1e-6 of the oracle: it evaluates the same formula in anothe
 form's and the factor 4 covers the four compounding steps; a wrong formula is off by 1e-3 or more.
 A fixed tolerance would be wrong for Ftrl's ``linear``, where acc'^p - acc^p cancels.
 
-Then: the bf16 gradient instances are bit-identical to the widened gradient, the slice protocol
-leaves every element outside the range untouched, unsupported operands are refused untouched, and
-the methods agree with their torch form end to end (LocalOptimizer, and the DistriOptimizer's
+Then: the bf16 gradient instances are bit-identical to the widened gradient, the device-counter
+forms of Adam and Adagrad follow their host-scalar forms, the slice protocol leaves every element
+outside the range untouched, unsupported operands are refused untouched by every wrapper, and the
+methods agree with their torch form end to end (LocalOptimizer, and the DistriOptimizer's
 sharded bf16 wire at world 1)."""
 import contextlib
 import copy
 import functools
+import math
 import os
 import socket
 
@@ -36,9 +38,11 @@ CASES = {
     "ftrl_p0.3": dict(kind="ftrl", lr=0.05, init=0.1, l1=1e-2, l2=1e-3, l2s=1e-4, power=-0.3),
     "ftrl_p0": dict(kind="ftrl", lr=0.05, init=0.1, l1=1e-2, l2=1e-3, l2s=1e-4, power=0.0),
     "ftrl_nol2s": dict(kind="ftrl", lr=0.05, init=0.1, l1=1e-2, l2=1e-3, l2s=0.0, power=-0.5),
+    "adam": dict(kind="adam", lr=1e-3, decay=0.001, b1=0.9, b2=0.999, eps=1e-8, wd=1e-3),
+    "adagrad": dict(kind="adagrad", lr=0.01, decay=0.001, wd=1e-3),
 }
 STATES = {"rmsprop": ("sumSquare",), "adadelta": ("paramVariance", "delta"), "adamax": ("m", "u"),
-          "ftrl": ("accum", "linear")}
+          "ftrl": ("accum", "linear"), "adam": ("s", "r"), "adagrad": ("paramVariance",)}
 
 
 def _native():
@@ -91,6 +95,19 @@ def _torch_form(hp, w, g, st, t):
         m.mul_(hp["b1"]).add_(g, alpha=1 - hp["b1"])
         torch.maximum(u * hp["b2"], g.abs() + hp["eps"], out=u)
         w.addcdiv_(m, u, value=-hp["lr"] / (1 - hp["b1"] ** (t + 1)))
+    elif k == "adam":  # ops/reference.py adam_step
+        m, v = st
+        g = g + hp["wd"] * w
+        m.mul_(hp["b1"]).add_(g, alpha=1 - hp["b1"])
+        v.mul_(hp["b2"]).addcmul_(g, g, value=1 - hp["b2"])
+        clr = hp["lr"] / (1 + t * hp["decay"])
+        step_size = clr * math.sqrt(1 - hp["b2"] ** (t + 1)) / (1 - hp["b1"] ** (t + 1))
+        w.addcdiv_(m, v.sqrt().add_(hp["eps"]), value=-step_size)
+    elif k == "adagrad":
+        (s,) = st
+        g = g + hp["wd"] * w
+        s.addcmul_(g, g)
+        w.addcdiv_(g, s.sqrt().add_(1e-10), value=-hp["lr"] / (1 + t * hp["decay"]))
     else:
         acc, lin = st
         gs = g + 2 * hp["l2s"] * w if hp["l2s"] > 0 else g
@@ -114,16 +131,25 @@ def _kernel_step(hp, w, g, st, t, shadow):
     if k == "adamax":
         return N.adamax_step(w, g, st[0], st[1], hp["lr"], hp["b1"], hp["b2"], hp["eps"], t + 1, SCALE, shadow)
     if k == "adam":
-        return N.adam_step(w, g, st[0], st[1], 1e-3, 0.9, 0.999, 1e-8, t + 1, 0.0, SCALE, shadow)
+        return N.adam_step(w, g, st[0], st[1], hp["lr"] / (1 + t * hp["decay"]), hp["b1"], hp["b2"], hp["eps"], t + 1,
+                           hp["wd"], SCALE, shadow)
+    if k == "adagrad":
+        return N.adagrad_step(w, g, st[0], hp["lr"], hp["decay"], t, hp["wd"], SCALE, shadow)
     return N.ftrl_step(w, g, st[0], st[1], hp["lr"], hp["power"], hp["l1"], hp["l2"], hp["l2s"], SCALE, shadow)
 
 
+def _grads16(grads, g16):
+    """The gradients the kernel and both references see: rounded to bf16 first when ``g16``."""
+    return [g.bfloat16() for g in grads] if g16 else grads
+
+
 @functools.lru_cache(maxsize=None)
-def _references(case, n):
+def _references(case, n, g16=False):
     """(oracle, torch_fp32): each ``[w, state...]`` after STEPS steps on the host, computed once per
     case and size and never modified."""
     hp = CASES[case]
     w0, grads = _inputs(n)
+    grads = _grads16(grads, g16)
     out = []
     for dtype in (torch.float64, torch.float32):
         w, st = w0.to(dtype), _init_states(hp, n, dtype)
@@ -136,9 +162,25 @@ def _references(case, n):
 @pytest.mark.parametrize("n", [1003, 3])
 @pytest.mark.parametrize("case", list(CASES))
 def test_kernel_within_four_times_the_torch_forms_error(case, n):
+    _check_against_oracle(case, n)
+
+
+# the smallest length at which the grid-stride loop of k_optim (2048 blocks of 256 lanes, four
+# elements each) runs a second pass, with a scalar tail: one full pass, 257 more float4s, one element
+N_TWO_PASSES = 2048 * 256 * 4 + 1029
+
+
+def test_grid_stride_second_pass_bf16_gradient():
+    """The i += stride pass: Adam (two states), the bf16 gradient and the shadow, same bound."""
+    _check_against_oracle("adam", N_TWO_PASSES, g16=True)
+
+
+def _check_against_oracle(case, n, g16=False):
     hp = CASES[case]
-    oracle, t32 = _references(case, n)
+    # the long case is used once: not kept in the cache
+    oracle, t32 = (_references.__wrapped__ if n > 10000 else _references)(case, n, g16)
     w0, grads = _inputs(n)
+    grads = _grads16(grads, g16)
     w = w0.to(dev)
     st = _init_states(hp, n, torch.float32, dev)
     shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
@@ -168,22 +210,19 @@ def test_kernel_within_four_times_the_torch_forms_error(case, n):
         assert 0 < zeros < n, zeros  # both sides of the l1 test ran
 
 
-BF16_CASES = ["rmsprop", "adadelta", "adamax", "ftrl_p0.5", "ftrl_p0.3", "adam"]
+BF16_CASES = ["rmsprop", "adadelta", "adamax", "ftrl_p0.5", "ftrl_p0.3", "adam", "adagrad"]
 
 
 @pytest.mark.parametrize("case", BF16_CASES)
 def test_bf16_gradient_is_the_widened_gradient_bit_for_bit(case):
-    hp = CASES.get(case, dict(kind="adam"))
+    hp = CASES[case]
     n = 1003
     w0, grads = _inputs(n)
     g16 = grads[1].bfloat16().to(dev)
     outs = []
     for g in (g16, g16.float()):
         w = w0.to(dev)
-        if hp["kind"] == "adam":
-            st = [torch.zeros(n, device=dev), torch.zeros(n, device=dev)]
-        else:
-            st = _init_states(hp, n, torch.float32, dev)
+        st = _init_states(hp, n, torch.float32, dev)
         shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
         assert _kernel_step(hp, w, g, st, 0, shadow) is not NotImplemented
         outs.append([w, shadow] + st)
@@ -193,7 +232,7 @@ def test_bf16_gradient_is_the_widened_gradient_bit_for_bit(case):
         assert torch.isfinite(a.float()).all() and torch.equal(a, b)
 
 
-SLICE_CASES = ["rmsprop", "adadelta", "adamax", "ftrl_p0.5"]
+SLICE_CASES = ["rmsprop", "adadelta", "adamax", "ftrl_p0.5", "adam", "adagrad"]
 
 
 @pytest.mark.parametrize("g_dtype", [torch.float32, torch.bfloat16])
@@ -240,6 +279,83 @@ def test_unsupported_operands_are_refused_untouched(case):
     # an fp16 gradient
     assert _kernel_step(hp, w, g.half(), states(), 0, None) is NotImplemented
     assert torch.equal(w, w0[:n])
+
+
+@pytest.mark.parametrize("n", [1003, 3])
+@pytest.mark.parametrize("case", ["adam", "adagrad"])
+def test_device_counter_form_follows_the_host_scalar_form(case, n):
+    """The iteration count read on the device (``prepare()`` of the rule forms the step size in
+    fp32) against the same kernel with the step size formed on the host in double."""
+    N = _native().native_ops
+    hp = CASES[case]
+    w0, grads = _inputs(n)
+    runs = []
+    for on_device in (False, True):
+        w, st = w0.to(dev), _init_states(hp, n, torch.float32, dev)
+        shadow = torch.zeros(n, dtype=torch.bfloat16, device=dev)
+        nt = torch.zeros(1, device=dev)
+        for t, g in enumerate(grads):
+            g = g.to(dev)
+            if not on_device:
+                r = _kernel_step(hp, w, g, st, t, shadow)
+            elif case == "adam":
+                r = N.adam_step_dev(w, g, st[0], st[1], nt, hp["lr"], hp["decay"], hp["b1"], hp["b2"], hp["eps"],
+                                    hp["wd"], SCALE, shadow)
+            else:  # the host count (here a wrong one) is ignored when dev_n is given
+                r = N.adagrad_step(w, g, st[0], hp["lr"], hp["decay"], 1000, hp["wd"], SCALE, shadow, dev_n=nt)
+            assert r is not NotImplemented
+            nt.add_(1)
+        torch.cuda.synchronize()
+        assert torch.equal(shadow, w.bfloat16())
+        runs.append([w] + st)
+    assert not torch.equal(runs[0][0].cpu(), w0)
+    for host, devc in zip(*runs):
+        torch.testing.assert_close(devc, host, rtol=1e-5, atol=1e-6)
+
+
+def _wrapper_calls():
+    """name -> (operand names, call(operands)) of the wrappers that share the operand contract with
+    the rule kernels but are not reached through ``_kernel_step``'s cases."""
+    N = _native().native_ops
+    nt = torch.zeros(1, device=dev)
+    return {
+        "sgd_step": (("w", "g", "buf", "shadow"),
+                     lambda o: N.sgd_step(o["w"], o["g"], o["buf"], 0.1, 0.9, 0.0, 1e-4, True, False, SCALE,
+                                          o["shadow"])),
+        "adam_step": (("w", "g", "m", "v", "shadow"),
+                      lambda o: N.adam_step(o["w"], o["g"], o["m"], o["v"], 1e-3, 0.9, 0.999, 1e-8, 1, 1e-3, SCALE,
+                                            o["shadow"])),
+        "adam_step_dev": (("w", "g", "m", "v", "shadow"),
+                          lambda o: N.adam_step_dev(o["w"], o["g"], o["m"], o["v"], nt, 1e-3, 0.0, 0.9, 0.999, 1e-8,
+                                                    1e-3, SCALE, o["shadow"])),
+        "adagrad_step": (("w", "g", "s", "shadow"),
+                         lambda o: N.adagrad_step(o["w"], o["g"], o["s"], 0.01, 0.0, 0, 1e-3, SCALE, o["shadow"])),
+    }
+
+
+@pytest.mark.parametrize("wrapper", ["sgd_step", "adam_step", "adam_step_dev", "adagrad_step"])
+def test_host_shadow_and_fp64_state_are_refused_untouched(wrapper):
+    """One contract for every wrapper: a shadow in host memory and a state that is not fp32 never
+    reach a kernel (it would read them as device bf16 / fp32), and no operand is written."""
+    n = 1003
+    names, call = _wrapper_calls()[wrapper]
+    gen = torch.Generator().manual_seed(11)
+
+    def operands():
+        o = {k: torch.rand(n, generator=gen).add_(0.1).to(dev) for k in names}
+        o["shadow"] = o["shadow"].bfloat16()
+        return o
+
+    state = names[2]
+    for bad, make in (("shadow", lambda t: t.cpu()), (state, lambda t: t.double())):
+        o = operands()
+        o[bad] = make(o[bad])
+        before = {k: v.clone() for k, v in o.items()}
+        assert call(o) is NotImplemented, (wrapper, bad)
+        torch.cuda.synchronize()
+        for k in names:
+            assert torch.equal(o[k], before[k]), (wrapper, bad, k)
+    assert call(operands()) is not NotImplemented  # the same operands, well-formed, are taken
 
 
 # ------------------------------------------------------------------------------------------- end to end

@@ -1,6 +1,8 @@
-"""Host side of the fused Adamax / Adadelta / RMSprop / Ftrl updates: the torch forms stay the CPU
-path (and the oracle of the kernels in tests/test_optim_fused.py), accept the bf16 wire gradient
-shard, and ``bigdl.optim.fused`` never changes what runs on the CPU."""
+"""Host side of the fused updates of the elementwise methods: the torch forms stay the CPU path (and
+the oracle of the kernels in tests/test_optim_fused.py), accept the bf16 wire gradient shard, and
+``bigdl.optim.fused`` never changes what runs on the CPU."""
+import pickle
+
 import pytest
 import torch
 
@@ -14,10 +16,12 @@ def _methods():
             "adadelta": lambda: O.Adadelta(decayrate=0.9, epsilon=1e-6),
             "adamax": lambda: O.Adamax(),
             "ftrl": lambda: O.Ftrl(learningrate=0.05, initial_accumulator_value=0.1, l1_regularization_strength=1e-2,
-                                   l2_regularization_strength=1e-3, l2_shrinkage_regularization_strength=1e-4)}
+                                   l2_regularization_strength=1e-3, l2_shrinkage_regularization_strength=1e-4),
+            "adam": lambda: O.Adam(learningrate=0.01, learningrate_decay=0.001),
+            "adagrad": lambda: O.Adagrad(learningrate=0.01, learningrate_decay=0.001, weightdecay=1e-3)}
 
 
-NAMES = ["rmsprop", "adadelta", "adamax", "ftrl"]
+NAMES = ["rmsprop", "adadelta", "adamax", "ftrl", "adam", "adagrad"]
 
 
 def _run(name, grads, steps):
@@ -85,3 +89,23 @@ def test_property_never_changes_the_cpu_path(name):
     assert torch.equal(on[0], off[0]) and torch.equal(on[1], off[1])
     for k in on[2]:
         assert torch.equal(on[2][k], off[2][k]), k
+
+
+def test_adam_pickled_before_a_step_reproduces_that_step():
+    """State keys, ``evalCounter`` and the per-iteration scalars survive a pickle: an Adam saved after
+    its first step and restored after the second was taken repeats the second step bit for bit."""
+    grads = _grads(2)
+    meth = _methods()["adam"]()
+    meth.grad_scale = SCALE
+    x = torch.randn(N, generator=torch.Generator().manual_seed(2))
+    meth.optimize(lambda _x: (0.0, grads[0]), x)
+    assert meth.state["evalCounter"] == 1 and {"s", "r"} <= set(meth.state)
+    blob, x1 = pickle.dumps(meth), x.clone()
+    meth.optimize(lambda _x: (0.0, grads[1]), x)
+    assert meth.state["evalCounter"] == 2 and not torch.equal(x, x1)
+    back = pickle.loads(blob)
+    assert back.state["evalCounter"] == 1
+    back.optimize(lambda _x: (0.0, grads[1]), x1)
+    assert back.state["evalCounter"] == 2 and torch.equal(x1, x)
+    for k in ("s", "r"):
+        assert torch.equal(back.state[k], meth.state[k]), k
