@@ -39,6 +39,12 @@ def base_parser(desc: str, batch: int, epochs: int, lr: float) -> argparse.Argum
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--threads", type=int, default=4, help="native loader worker threads")
     ap.add_argument("--saveModel", default=None, help="write the trained model here (.bigdl)")
+    ap.add_argument("--gradientL2NormThreshold", type=float, default=None,
+                    help="scale the gradient so that its global L2 norm does not exceed this")
+    ap.add_argument("--gradientMin", type=float, default=None,
+                    help="clamp every gradient element from below (needs --gradientMax too)")
+    ap.add_argument("--gradientMax", type=float, default=None,
+                    help="clamp every gradient element from above (needs --gradientMin too)")
     return ap
 
 
@@ -116,6 +122,7 @@ def assemble(model, train_set, criterion, optim, args, val_set=None, vmethods: O
     opt.setEndWhen(end)
     if args.checkpoint:
         opt.setCheckpoint(args.checkpoint, Trigger.everyEpoch(), args.overwrite)
+    set_gradient_clipping(opt, args)
     if val_set is not None and vmethods:
         opt.setValidation(Trigger.everyEpoch(), val_set, list(vmethods), batch or args.batchSize)
     if args.summary:
@@ -125,6 +132,18 @@ def assemble(model, train_set, criterion, optim, args, val_set=None, vmethods: O
         opt.setTrainSummary(ts)
         if val_set is not None:
             opt.setValidationSummary(ValidationSummary(args.summary, name))
+    return opt
+
+
+def set_gradient_clipping(opt, args):
+    """``models/inception/Train.scala:111-117``: the constant clamp only when both bounds are given,
+    the L2-norm threshold on its own."""
+    lo, hi = getattr(args, "gradientMin", None), getattr(args, "gradientMax", None)
+    if lo is not None and hi is not None:
+        opt.setConstantGradientClipping(lo, hi)
+    thr = getattr(args, "gradientL2NormThreshold", None)
+    if thr is not None:
+        opt.setGradientClippingByl2Norm(thr)
     return opt
 
 

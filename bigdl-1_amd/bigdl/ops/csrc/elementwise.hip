@@ -187,76 +187,36 @@ BIGDL_EXPORT int bigdl_threshold_bwd_f32(const void* gy, const void* ref, void* 
 //   d = nesterov ? g' + mom*v : v (or g' when mom == 0) ; w -= lr * (lrs ? lrs*d : d) ;
 //   shadow = bf16(w)
 // ------------------------------------------------------------------------------------------------
-template <typename GT, bool MOM, bool NEST, bool FIRST, bool SHADOW, bool PERELEM>
-__global__ void k_sgd(float* __restrict__ w, const GT* __restrict__ g, float* __restrict__ buf,
-                      bf16_t* __restrict__ shadow, const float* __restrict__ lrs, const float* __restrict__ wds,
-                      long long n4, float lr, float mom, float damp, float wd, float scale, int tail,
-                      const float* __restrict__ first_dev) {
-  long long stride = (long long)gridDim.x * blockDim.x;
-  // first-iteration rule (v = g) from the template or, in HIP-graph mode, from a device flag the
-  // captured step clears after the update (so a replayed graph can start a fresh trajectory)
-  const bool first = FIRST || (first_dev != nullptr && *first_dev != 0.f);
-  if (blockIdx.x == 0 && threadIdx.x < tail) {
-    // the n % 4 trailing elements (scalar; the arena slice need not be a multiple of 4)
-    const long long e = n4 * 4 + threadIdx.x;
-    const float wv = w[e];
-    const float gg = g_at(g, e) * scale + wd * (PERELEM && wds ? wds[e] : 1.f) * wv;
-    float d = gg;
-    if (MOM) {
-      const float b = first ? gg : mom * buf[e] + (1.f - damp) * gg;
-      buf[e] = b;
-      d = NEST ? gg + mom * b : b;
-    }
-    const float nw = wv - lr * (PERELEM && lrs ? lrs[e] : 1.f) * d;
-    w[e] = nw;
-    if (SHADOW) shadow[e] = f2bf(nw);
-  }
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 W = reinterpret_cast<float4*>(w)[i];
-    float wv[4] = {W.x, W.y, W.z, W.w};
-    float gv[4];
-    g_load4(g, i, gv);
-    float wdv[4] = {1.f, 1.f, 1.f, 1.f};
-    float lrv[4] = {1.f, 1.f, 1.f, 1.f};
-    if (PERELEM) {
-      if (wds) {
-        float4 t = reinterpret_cast<const float4*>(wds)[i];
-        wdv[0] = t.x; wdv[1] = t.y; wdv[2] = t.z; wdv[3] = t.w;
-      }
-      if (lrs) {
-        float4 t = reinterpret_cast<const float4*>(lrs)[i];
-        lrv[0] = t.x; lrv[1] = t.y; lrv[2] = t.z; lrv[3] = t.w;
-      }
-    }
-    float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (MOM && !first) {
-      float4 B = reinterpret_cast<float4*>(buf)[i];
-      bv[0] = B.x; bv[1] = B.y; bv[2] = B.z; bv[3] = B.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float gg = gv[k] * scale + wd * wdv[k] * wv[k];
-      float d = gg;
-      if (MOM) {
-        bv[k] = first ? gg : mom * bv[k] + (1.f - damp) * gg;
-        d = NEST ? gg + mom * bv[k] : bv[k];
-      }
-      wv[k] -= lr * lrv[k] * d;
-    }
-    reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    if (MOM) reinterpret_cast<float4*>(buf)[i] = make_float4(bv[0], bv[1], bv[2], bv[3]);
-    if (SHADOW) store_shadow4(shadow, i, wv);
-  }
-}
+#define K_SGD_NAME k_sgd
+#define K_SGD_CLIP 0
+#define K_SGD_CLIP_PARAMS
+#include "k_sgd.inc.h"
+#undef K_SGD_NAME
+#undef K_SGD_CLIP
+#undef K_SGD_CLIP_PARAMS
+// the same pass with the gradient clipped right after the load (GradClip, optim_common.h)
+#define K_SGD_NAME k_sgd_clip
+#define K_SGD_CLIP 1
+#define K_SGD_CLIP_PARAMS , GradClip c, float one
+#include "k_sgd.inc.h"
+#undef K_SGD_NAME
+#undef K_SGD_CLIP
+#undef K_SGD_CLIP_PARAMS
 
-#define SGD_LAUNCH(M, NS, F, SH, PE)                                                                    \
-  hipLaunchKernelGGL((k_sgd<GT, M, NS, F, SH, PE>), dim3(grid), dim3(256), 0, s, w, g, buf, shadow, lrs, wds, n4, \
-                     lr, mom, damp, wd, scale, tail, first_dev)
+#define SGD_LAUNCH(M, NS, F, SH, PE)                                                                            \
+  do {                                                                                                          \
+    if (clip)                                                                                                   \
+      hipLaunchKernelGGL((k_sgd_clip<GT, M, NS, F, SH, PE>), dim3(grid), dim3(256), 0, s, w, g, buf, shadow, lrs, \
+                         wds, n4, lr, mom, damp, wd, scale, tail, first_dev, *clip, 1.f);                       \
+    else                                                                                                        \
+      hipLaunchKernelGGL((k_sgd<GT, M, NS, F, SH, PE>), dim3(grid), dim3(256), 0, s, w, g, buf, shadow, lrs, wds, \
+                         n4, lr, mom, damp, wd, scale, tail, first_dev);                                        \
+  } while (0)
 
 template <typename GT>
 static int sgd_impl(float* w, const GT* g, float* buf, bf16_t* shadow, const float* lrs, const float* wds,
                     long long n, float lr, float mom, float damp, float wd, int nesterov, int first, float scale,
-                    const float* first_dev, hipStream_t s) {
+                    const float* first_dev, hipStream_t s, const GradClip* clip = nullptr) {
   if (n <= 0) return 0;
   const long long n4 = n / 4;
   const int tail = (int)(n & 3);
@@ -307,6 +267,19 @@ BIGDL_EXPORT int bigdl_sgd_g16(float* w, const bf16_t* g, float* buf, bf16_t* sh
                                const float* wds, long long n, float lr, float mom, float damp, float wd, int nesterov,
                                int first, float scale, const float* first_dev, hipStream_t s) {
   return sgd_impl<bf16_t>(w, g, buf, shadow, lrs, wds, n, lr, mom, damp, wd, nesterov, first, scale, first_dev, s);
+}
+
+// either gradient type with a GradClip operand: sumsq null = no L2 clip, lo / hi = -inf / +inf = no clamp
+BIGDL_EXPORT int bigdl_sgd_clip(float* w, const void* g, int g16, float* buf, bf16_t* shadow, const float* lrs,
+                                const float* wds, long long n, float lr, float mom, float damp, float wd, int nesterov,
+                                int first, float scale, const float* first_dev, const float* sumsq, float threshold,
+                                float lo, float hi, hipStream_t s) {
+  const GradClip c{sumsq, threshold, lo, hi};
+  if (g16)
+    return sgd_impl<bf16_t>(w, (const bf16_t*)g, buf, shadow, lrs, wds, n, lr, mom, damp, wd, nesterov, first, scale,
+                            first_dev, s, &c);
+  return sgd_impl<float>(w, (const float*)g, buf, shadow, lrs, wds, n, lr, mom, damp, wd, nesterov, first, scale,
+                         first_dev, s, &c);
 }
 
 // ------------------------------------------------------------------------------------------------

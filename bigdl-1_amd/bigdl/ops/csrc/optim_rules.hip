@@ -7,6 +7,9 @@
 // weight as one 8-B store.  HBM-bound: 16 B per lane per access, grid capped at 2048 blocks of 256
 // (cdna_hip_programming.md Guideline 11).
 //
+// k_optim_clip is the same pass with a GradClip operand (optim_common.h): the gradient is clamped and
+// L2-scaled right after the load, and the rule runs with scale 1.  k_optim itself is unchanged by it.
+//
 // A rule is a struct of its hyper-parameters (by value in the kernel arguments) with
 //   NS                     number of fp32 state tensors (1 or 2)
 //   prepare()              called once per thread on the kernel's copy before the loop: Adam and
@@ -137,38 +140,21 @@ struct AdagradRule {
 // the kernel: w, s0, s1 16-B aligned, g 16-B (fp32) or 8-B (bf16), shadow 8-B (host-checked);
 // s1 is not touched when the rule has one state
 // ------------------------------------------------------------------------------------------------
-template <typename R, typename G>
-__global__ void k_optim(R r, float* __restrict__ w, const G* __restrict__ g, float* __restrict__ s0,
-                        float* __restrict__ s1, bf16_t* __restrict__ shadow, long long n4, int tail) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  r.prepare();
-  if (blockIdx.x == 0 && threadIdx.x < tail) {
-    const long long e = n4 * 4 + threadIdx.x;
-    float nw = w[e], a = s0[e], b = 0.f;
-    if (R::NS > 1) b = s1[e];
-    r.step(nw, g_at(g, e), a, b);
-    w[e] = nw;
-    s0[e] = a;
-    if (R::NS > 1) s1[e] = b;
-    if (shadow) shadow[e] = f2bf(nw);
-  }
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 W = reinterpret_cast<float4*>(w)[i];
-    const float4 A = reinterpret_cast<float4*>(s0)[i];
-    float wv[4] = {W.x, W.y, W.z, W.w}, gv[4], av[4] = {A.x, A.y, A.z, A.w}, bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (R::NS > 1) {
-      const float4 B = reinterpret_cast<float4*>(s1)[i];
-      bv[0] = B.x; bv[1] = B.y; bv[2] = B.z; bv[3] = B.w;
-    }
-    g_load4(g, i, gv);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r.step(wv[k], gv[k], av[k], bv[k]);
-    reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    reinterpret_cast<float4*>(s0)[i] = make_float4(av[0], av[1], av[2], av[3]);
-    if (R::NS > 1) reinterpret_cast<float4*>(s1)[i] = make_float4(bv[0], bv[1], bv[2], bv[3]);
-    if (shadow) store_shadow4(shadow, i, wv);
-  }
-}
+#define K_OPTIM_NAME k_optim
+#define K_OPTIM_CLIP 0
+#define K_OPTIM_CLIP_PARAMS
+#include "k_optim.inc.h"
+#undef K_OPTIM_NAME
+#undef K_OPTIM_CLIP
+#undef K_OPTIM_CLIP_PARAMS
+// the same pass with the gradient clipped right after the load (GradClip, optim_common.h)
+#define K_OPTIM_NAME k_optim_clip
+#define K_OPTIM_CLIP 1
+#define K_OPTIM_CLIP_PARAMS , GradClip c, float cscale
+#include "k_optim.inc.h"
+#undef K_OPTIM_NAME
+#undef K_OPTIM_CLIP
+#undef K_OPTIM_CLIP_PARAMS
 
 template <typename R, typename G>
 static int optim_launch(const R& r, float* w, const G* g, float* s0, float* s1, bf16_t* shadow, long long n,
@@ -178,6 +164,26 @@ static int optim_launch(const R& r, float* w, const G* g, float* s0, float* s1, 
   hipLaunchKernelGGL((k_optim<R, G>), dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, r, w, g, s0, s1,
                      shadow, n4, (int)(n & 3));
   BIGDL_CHECK_LAUNCH();
+}
+
+template <typename R, typename G>
+static int optim_launch_clip(R r, float* w, const G* g, float* s0, float* s1, bf16_t* shadow, long long n,
+                             const GradClip& c, hipStream_t s) {
+  if (n <= 0) return 0;
+  const long long n4 = n / 4;
+  const float scale = r.scale;
+  r.scale = 1.f;
+  hipLaunchKernelGGL((k_optim_clip<R, G>), dim3(bigdl_grid(n4 > 0 ? n4 : 1, 256)), dim3(256), 0, s, r, w, g, s0, s1,
+                     shadow, n4, (int)(n & 3), c, scale);
+  BIGDL_CHECK_LAUNCH();
+}
+
+// a clipped launch of either gradient type: the _clip entry points take (g, g16) like the LARS ones
+template <typename R>
+static int optim_clip(const R& r, float* w, const void* g, int g16, float* s0, float* s1, bf16_t* shadow,
+                      long long n, const GradClip& c, hipStream_t s) {
+  if (g16) return optim_launch_clip(r, w, (const bf16_t*)g, s0, s1, shadow, n, c, s);
+  return optim_launch_clip(r, w, (const float*)g, s0, s1, shadow, n, c, s);
 }
 
 template <typename G>
@@ -260,4 +266,54 @@ BIGDL_EXPORT int bigdl_adagrad(float* w, const float* g, float* sv, bf16_t* shad
 BIGDL_EXPORT int bigdl_adagrad_g16(float* w, const bf16_t* g, float* sv, bf16_t* shadow, long long n, float clr,
                                    const float* dev_n, float lr, float lr_decay, float wd, float scale, hipStream_t s) {
   return optim_launch(AdagradRule{scale, clr, wd, dev_n, lr, lr_decay}, w, g, sv, (float*)nullptr, shadow, n, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// clipped entry points: the same updates with a GradClip operand (optim_common.h); g is fp32, or
+// bf16 when g16 is set.  sumsq null = no L2 clip; lo / hi = -inf / +inf = no clamp.
+// ------------------------------------------------------------------------------------------------
+BIGDL_EXPORT int bigdl_rmsprop_clip(float* w, const void* g, int g16, float* sq, bf16_t* shadow, long long n,
+                                    float clr, float dr, float omdr, float eps, float scale, const float* sumsq,
+                                    float threshold, float lo, float hi, hipStream_t s) {
+  return optim_clip(RmspropRule{scale, clr, dr, omdr, eps}, w, g, g16, sq, (float*)nullptr, shadow, n,
+                    GradClip{sumsq, threshold, lo, hi}, s);
+}
+
+BIGDL_EXPORT int bigdl_adadelta_clip(float* w, const void* g, int g16, float* v, float* d, bf16_t* shadow, long long n,
+                                     float dr, float omdr, float eps, float scale, const float* sumsq,
+                                     float threshold, float lo, float hi, hipStream_t s) {
+  return optim_clip(AdadeltaRule{scale, dr, omdr, eps}, w, g, g16, v, d, shadow, n, GradClip{sumsq, threshold, lo, hi},
+                    s);
+}
+
+BIGDL_EXPORT int bigdl_adamax_clip(float* w, const void* g, int g16, float* m, float* u, bf16_t* shadow, long long n,
+                                   float step, float b1, float omb1, float b2, float eps, float scale,
+                                   const float* sumsq, float threshold, float lo, float hi, hipStream_t s) {
+  return optim_clip(AdamaxRule{scale, step, b1, omb1, b2, eps}, w, g, g16, m, u, shadow, n,
+                    GradClip{sumsq, threshold, lo, hi}, s);
+}
+
+BIGDL_EXPORT int bigdl_ftrl_clip(float* w, const void* g, int g16, float* acc, float* lin, bf16_t* shadow, long long n,
+                                 float lr, float p, float l1, float two_l2, float two_l2s, float scale,
+                                 const float* sumsq, float threshold, float lo, float hi, hipStream_t s) {
+  const GradClip c{sumsq, threshold, lo, hi};
+  if (p == 0.5f) return optim_clip(FtrlRule<0>{scale, lr, p, l1, two_l2, two_l2s}, w, g, g16, acc, lin, shadow, n, c, s);
+  if (p == 0.f) return optim_clip(FtrlRule<1>{scale, lr, p, l1, two_l2, two_l2s}, w, g, g16, acc, lin, shadow, n, c, s);
+  return optim_clip(FtrlRule<2>{scale, lr, p, l1, two_l2, two_l2s}, w, g, g16, acc, lin, shadow, n, c, s);
+}
+
+// dev_n nullable: with it the step size is formed on the device (bigdl_adam_dev) and step_size is ignored
+BIGDL_EXPORT int bigdl_adam_clip(float* w, const void* g, int g16, float* m, float* v, bf16_t* shadow, long long n,
+                                 float step_size, const float* dev_n, float lr, float lr_decay, float b1, float b2,
+                                 float eps, float wd, float scale, const float* sumsq, float threshold, float lo,
+                                 float hi, hipStream_t s) {
+  return optim_clip(AdamRule{scale, step_size, b1, b2, eps, wd, dev_n, lr, lr_decay}, w, g, g16, m, v, shadow, n,
+                    GradClip{sumsq, threshold, lo, hi}, s);
+}
+
+BIGDL_EXPORT int bigdl_adagrad_clip(float* w, const void* g, int g16, float* sv, bf16_t* shadow, long long n, float clr,
+                                    const float* dev_n, float lr, float lr_decay, float wd, float scale,
+                                    const float* sumsq, float threshold, float lo, float hi, hipStream_t s) {
+  return optim_clip(AdagradRule{scale, clr, wd, dev_n, lr, lr_decay}, w, g, g16, sv, (float*)nullptr, shadow, n,
+                    GradClip{sumsq, threshold, lo, hi}, s);
 }

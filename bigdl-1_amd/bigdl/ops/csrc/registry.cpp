@@ -10,6 +10,7 @@ static const char* kOps[] = {
     "lars_sumsq", "lars_fold", "lars_sgd",
     "concat_fwd", "concat_split_bwd", "sum_n",
     "rmsprop", "adadelta", "adamax", "ftrl", "adam_g16",
+    "grad_sumsq", "sgd_clip", "optim_clip",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

@@ -1844,7 +1844,7 @@ def _wgrad_async_or_inline(x, gy, w4, gw_acc, scale, stride, pad, dilation, pad_
 
 
 # ------------------------------------------------------------------------------------------------ optimizers
-def _rule_ok(w, g, states, shadow, extra=()):
+def _rule_ok(w, g, states, shadow, extra=(), clip=None):
     """The operand contract of every update kernel (csrc/elementwise.hip k_sgd, optim_rules.hip,
     lars.hip), in one place, so that a mis-shaped launch never reaches the GPU:
 
@@ -1852,9 +1852,11 @@ def _rule_ok(w, g, states, shadow, extra=()):
       device, contiguous, as long as ``w``, 16-B aligned;
     * ``g``: fp32 (16-B aligned) or bf16 (the wire shard, 8-B aligned), device, contiguous, same length;
     * ``shadow``: bf16, device, contiguous, same length, 8-B aligned;
-    * ``extra`` (iteration counters and flags the kernel reads): fp32 on the device.
+    * ``extra`` (iteration counters and flags the kernel reads): fp32 on the device;
+    * ``clip`` (a :class:`bigdl.parameters.GradClip`): its ``sumsq``, when it has an L2 threshold, is
+      fp32, on the device, one element.
 
-    ``None`` among ``states``, ``extra`` and for ``shadow`` means the operand is not passed."""
+    ``None`` among ``states``, ``extra`` and for ``shadow`` / ``clip`` means the operand is not passed."""
     n = w.numel()
 
     def vec(t, dtypes, align):
@@ -1867,7 +1869,21 @@ def _rule_ok(w, g, states, shadow, extra=()):
         return False
     if shadow is not None and not vec(shadow, (_bf16,), 8):
         return False
+    if clip is not None and clip.threshold is not None:
+        sq = clip.sumsq
+        if not (isinstance(sq, torch.Tensor) and sq.is_cuda and sq.dtype == _f32 and sq.numel() == 1):
+            return False
     return all(t.is_cuda and t.dtype == _f32 for t in extra if t is not None)
+
+
+def _clip_args(clip):
+    """The GradClip operand of a ``_clip`` entry point: (sumsq pointer or null, threshold, lo, hi)."""
+    sq, thr, lo, hi = clip.operands()
+    return ptr(sq), _f(thr), _f(lo), _f(hi)
+
+
+def _g16(g):
+    return C.c_int(int(g.dtype == _bf16))
 
 
 def _entry(name, g):
@@ -1877,17 +1893,53 @@ def _entry(name, g):
 
 @register("sgd_step")
 def sgd_step(w, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_step, grad_scale=1.0, shadow=None,
-             lrs=None, wds=None, first_dev=None):
+             lrs=None, wds=None, first_dev=None, clip=None):
     """Fused SGD over a flat fp32 slice; ``g`` is fp32 or bf16 (the bf16-wire reduce-scatter output,
-    read directly by the kernel instead of being unpacked into an fp32 shard first)."""
+    read directly by the kernel instead of being unpacked into an fp32 shard first).  ``clip`` (a
+    GradClip) clips ``g·grad_scale`` inside the same pass (bigdl_sgd_clip)."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (buf, lrs, wds), shadow, (first_dev,)) or (momentum != 0 and buf is None):
+    if not _rule_ok(w, g, (buf, lrs, wds), shadow, (first_dev,), clip) or (momentum != 0 and buf is None):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_sgd_clip(ptr(w), ptr(g), _g16(g), ptr(buf if momentum != 0 else None), ptr(shadow),
+                                    ptr(lrs), ptr(wds), _ll(w.numel()), _f(lr), _f(momentum), _f(dampening),
+                                    _f(weight_decay), C.c_int(int(bool(nesterov))), C.c_int(int(bool(first_step))),
+                                    _f(grad_scale), ptr(first_dev), *_clip_args(clip), _s()), "sgd_clip")
+        return w
     check(_entry("bigdl_sgd", g)(ptr(w), ptr(g), ptr(buf if momentum != 0 else None), ptr(shadow), ptr(lrs), ptr(wds),
                                  _ll(w.numel()), _f(lr), _f(momentum), _f(dampening), _f(weight_decay),
                                  C.c_int(int(bool(nesterov))), C.c_int(int(bool(first_step))), _f(grad_scale),
                                  ptr(first_dev), _s()), "sgd")
     return w
+
+
+#: floats of scratch ``grad_sumsq`` needs: one partial per workgroup, the grid is capped at 2048
+SUMSQ_PARTIALS = 2048
+
+
+@register("grad_sumsq")
+def grad_sumsq(g, out=None, partials=None):
+    """Σg² of a flat gradient (bigdl_grad_sumsq: one partial per workgroup, then one fixed-order sum
+    by a single wave; no float atomics, so the result is bitwise reproducible).  ``g`` is fp32
+    (16-B aligned) or the bf16 wire shard (8-B aligned, squared after widening).  ``out`` (fp32 [1])
+    and ``partials`` (fp32, at least ``SUMSQ_PARTIALS``) belong to the caller, who allocates them
+    once; they are created here only when not given.  Returns ``out``."""
+    if not (g.is_cuda and g.dtype in (_f32, _bf16) and g.is_contiguous()
+            and g.data_ptr() % (8 if g.dtype == _bf16 else 16) == 0 and hasattr(_lib(), "bigdl_grad_sumsq")):
+        return NotImplemented
+    for t, m in ((out, 1), (partials, SUMSQ_PARTIALS)):
+        if t is not None and not (t.is_cuda and t.dtype == _f32 and t.is_contiguous() and t.numel() >= m
+                                  and t.device == g.device):
+            return NotImplemented
+    if out is not None and out.numel() != 1:
+        return NotImplemented
+    if out is None:
+        out = torch.empty(1, dtype=_f32, device=g.device)
+    if partials is None:
+        partials = torch.empty(SUMSQ_PARTIALS, dtype=_f32, device=g.device)
+    check(_lib().bigdl_grad_sumsq(ptr(g), _g16(g), _ll(g.numel()), ptr(partials), C.c_int(partials.numel()), ptr(out),
+                                  _s()), "grad_sumsq")
+    return out
 
 
 def _lars_table_ok(table, w):
@@ -1933,26 +1985,37 @@ def lars_step(w, g, v, table, sums, hyper, grad_scale=1.0, shadow=None, c0=0, c1
 
 
 @register("adam_step")
-def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None):
+def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None, clip=None):
     """Fused Adam (bigdl_adam); ``step`` is the 1-based iteration, the bias-corrected step size is
     formed here.  ``g`` is fp32 or bf16 (the bf16 wire shard, widened on load)."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (m, v), shadow):
+    if not _rule_ok(w, g, (m, v), shadow, clip=clip):
         return NotImplemented
     step_size = lr * math.sqrt(1 - beta2 ** step) / (1 - beta1 ** step)
+    if clip is not None:
+        check(_lib().bigdl_adam_clip(ptr(w), ptr(g), _g16(g), ptr(m), ptr(v), ptr(shadow), _ll(w.numel()),
+                                     _f(step_size), ptr(None), _f(0.0), _f(0.0), _f(beta1), _f(beta2), _f(eps),
+                                     _f(weight_decay), _f(grad_scale), *_clip_args(clip), _s()), "adam_clip")
+        return w
     check(_entry("bigdl_adam", g)(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(w.numel()), _f(step_size),
                                   _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _f(grad_scale), _s()), "adam")
     return w
 
 
 @register("adam_step_dev")
-def adam_step_dev(w, g, m, v, dev_n, lr, lr_decay, beta1, beta2, eps, weight_decay=0.0, grad_scale=1.0, shadow=None):
+def adam_step_dev(w, g, m, v, dev_n, lr, lr_decay, beta1, beta2, eps, weight_decay=0.0, grad_scale=1.0, shadow=None,
+                  clip=None):
     """Adam whose iteration count ``dev_n`` (fp32 [1], before this step) is read on the device —
     the replay-safe form for HIP-graph capture; the caller advances ``dev_n`` afterwards.  fp32
     gradient only."""
     F3.mark_dirty(w)
-    if g.dtype != _f32 or dev_n is None or not _rule_ok(w, g, (m, v), shadow, (dev_n,)):
+    if g.dtype != _f32 or dev_n is None or not _rule_ok(w, g, (m, v), shadow, (dev_n,), clip):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_adam_clip(ptr(w), ptr(g), _g16(g), ptr(m), ptr(v), ptr(shadow), _ll(w.numel()), _f(0.0),
+                                     ptr(dev_n), _f(lr), _f(lr_decay), _f(beta1), _f(beta2), _f(eps),
+                                     _f(weight_decay), _f(grad_scale), *_clip_args(clip), _s()), "adam_clip")
+        return w
     check(_lib().bigdl_adam_dev(ptr(w), ptr(g), ptr(m), ptr(v), ptr(shadow), _ll(w.numel()), ptr(dev_n), _f(lr),
                                 _f(lr_decay), _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _f(grad_scale), _s()),
           "adam_dev")
@@ -1960,13 +2023,18 @@ def adam_step_dev(w, g, m, v, dev_n, lr, lr_decay, beta1, beta2, eps, weight_dec
 
 
 @register("adagrad_step")
-def adagrad_step(w, g, s, lr, lr_decay, n, weight_decay=0.0, grad_scale=1.0, shadow=None, dev_n=None):
+def adagrad_step(w, g, s, lr, lr_decay, n, weight_decay=0.0, grad_scale=1.0, shadow=None, dev_n=None, clip=None):
     """Fused Adagrad update (bigdl_adagrad); ``dev_n`` (fp32 [1] on the device, the iteration count
     before this step) makes it replay-safe under HIP-graph capture, else ``n`` (host) is used.
     ``g`` is fp32 or the bf16 wire shard."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (s,), shadow, (dev_n,)):
+    if not _rule_ok(w, g, (s,), shadow, (dev_n,), clip):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_adagrad_clip(ptr(w), ptr(g), _g16(g), ptr(s), ptr(shadow), _ll(w.numel()),
+                                        _f(lr / (1 + n * lr_decay)), ptr(dev_n), _f(lr), _f(lr_decay),
+                                        _f(weight_decay), _f(grad_scale), *_clip_args(clip), _s()), "adagrad_clip")
+        return w
     check(_entry("bigdl_adagrad", g)(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(w.numel()), _f(lr / (1 + n * lr_decay)),
                                      ptr(dev_n), _f(lr), _f(lr_decay), _f(weight_decay), _f(grad_scale), _s()),
           "adagrad")
@@ -1974,12 +2042,17 @@ def adagrad_step(w, g, s, lr, lr_decay, n, weight_decay=0.0, grad_scale=1.0, sha
 
 
 @register("rmsprop_step")
-def rmsprop_step(w, g, s, clr, decay_rate, eps, grad_scale=1.0, shadow=None):
+def rmsprop_step(w, g, s, clr, decay_rate, eps, grad_scale=1.0, shadow=None, clip=None):
     """Fused RMSprop update (bigdl_rmsprop): s = dr·s + (1-dr)·g'², w -= clr·g'/(sqrt(s) + eps) with
     g' = grad_scale·g, one pass over w, g, s and the bf16 shadow; ``g`` fp32 or the bf16 wire shard."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (s,), shadow):
+    if not _rule_ok(w, g, (s,), shadow, clip=clip):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_rmsprop_clip(ptr(w), ptr(g), _g16(g), ptr(s), ptr(shadow), _ll(w.numel()), _f(clr),
+                                        _f(decay_rate), _f(1 - decay_rate), _f(eps), _f(grad_scale),
+                                        *_clip_args(clip), _s()), "rmsprop_clip")
+        return w
     fn = _entry("bigdl_rmsprop", g)
     check(fn(ptr(w), ptr(g), ptr(s), ptr(shadow), _ll(w.numel()), _f(clr), _f(decay_rate), _f(1 - decay_rate),
              _f(eps), _f(grad_scale), _s()), "rmsprop")
@@ -1987,12 +2060,17 @@ def rmsprop_step(w, g, s, clr, decay_rate, eps, grad_scale=1.0, shadow=None):
 
 
 @register("adadelta_step")
-def adadelta_step(w, g, v, d, decay_rate, eps, grad_scale=1.0, shadow=None):
+def adadelta_step(w, g, v, d, decay_rate, eps, grad_scale=1.0, shadow=None, clip=None):
     """Fused Adadelta update (bigdl_adadelta) over w, g, the squared-gradient average ``v`` and the
     squared-update average ``d``."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (v, d), shadow):
+    if not _rule_ok(w, g, (v, d), shadow, clip=clip):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_adadelta_clip(ptr(w), ptr(g), _g16(g), ptr(v), ptr(d), ptr(shadow), _ll(w.numel()),
+                                         _f(decay_rate), _f(1 - decay_rate), _f(eps), _f(grad_scale),
+                                         *_clip_args(clip), _s()), "adadelta_clip")
+        return w
     fn = _entry("bigdl_adadelta", g)
     check(fn(ptr(w), ptr(g), ptr(v), ptr(d), ptr(shadow), _ll(w.numel()), _f(decay_rate), _f(1 - decay_rate),
              _f(eps), _f(grad_scale), _s()), "adadelta")
@@ -2000,12 +2078,17 @@ def adadelta_step(w, g, v, d, decay_rate, eps, grad_scale=1.0, shadow=None):
 
 
 @register("adamax_step")
-def adamax_step(w, g, m, u, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=None):
+def adamax_step(w, g, m, u, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=None, clip=None):
     """Fused Adamax update (bigdl_adamax); ``step`` is the 1-based iteration, the bias-corrected
     rate lr / (1 - beta1^step) is formed here.  ``eps`` may be a subnormal fp32 (the default 1e-38)."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (m, u), shadow):
+    if not _rule_ok(w, g, (m, u), shadow, clip=clip):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_adamax_clip(ptr(w), ptr(g), _g16(g), ptr(m), ptr(u), ptr(shadow), _ll(w.numel()),
+                                       _f(lr / (1 - beta1 ** step)), _f(beta1), _f(1 - beta1), _f(beta2), _f(eps),
+                                       _f(grad_scale), *_clip_args(clip), _s()), "adamax_clip")
+        return w
     fn = _entry("bigdl_adamax", g)
     check(fn(ptr(w), ptr(g), ptr(m), ptr(u), ptr(shadow), _ll(w.numel()), _f(lr / (1 - beta1 ** step)), _f(beta1),
              _f(1 - beta1), _f(beta2), _f(eps), _f(grad_scale), _s()), "adamax")
@@ -2013,12 +2096,17 @@ def adamax_step(w, g, m, u, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=
 
 
 @register("ftrl_step")
-def ftrl_step(w, g, accum, linear, lr, lr_power, l1, l2, l2_shrinkage, grad_scale=1.0, shadow=None):
+def ftrl_step(w, g, accum, linear, lr, lr_power, l1, l2, l2_shrinkage, grad_scale=1.0, shadow=None, clip=None):
     """Fused FTRL-proximal update (bigdl_ftrl) in the form of ``Ftrl._update``; ``lr_power`` is the
     (non-positive) learningRatePower."""
     F3.mark_dirty(w)
-    if not _rule_ok(w, g, (accum, linear), shadow):
+    if not _rule_ok(w, g, (accum, linear), shadow, clip=clip):
         return NotImplemented
+    if clip is not None:
+        check(_lib().bigdl_ftrl_clip(ptr(w), ptr(g), _g16(g), ptr(accum), ptr(linear), ptr(shadow), _ll(w.numel()),
+                                     _f(lr), _f(-lr_power), _f(l1), _f(2 * l2), _f(2 * l2_shrinkage), _f(grad_scale),
+                                     *_clip_args(clip), _s()), "ftrl_clip")
+        return w
     fn = _entry("bigdl_ftrl", g)
     check(fn(ptr(w), ptr(g), ptr(accum), ptr(linear), ptr(shadow), _ll(w.numel()), _f(lr), _f(-lr_power), _f(l1),
              _f(2 * l2), _f(2 * l2_shrinkage), _f(grad_scale), _s()), "ftrl")

@@ -620,13 +620,16 @@ def cross_entropy_fused(x, target_1b, weights=None, size_average=True, padding_v
 
 # ------------------------------------------------------------------------- optimizer
 def sgd_step(w, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_step, grad_scale=1.0,
-             shadow=None, lrs=None, wds=None, first_dev=None):
+             shadow=None, lrs=None, wds=None, first_dev=None, clip=None):
     """Fused SGD (``DL/optim/SGD.scala:61-124``): g += wd·x; v = μv + (1-d)g; nesterov; x -= lr·v.
 
     ``grad_scale`` folds the 1/N gradient averaging in; ``lrs``/``wds`` are per-element
-    learning-rate / weight-decay multipliers (``learningRates``/``weightDecays``)."""
+    learning-rate / weight-decay multipliers (``learningRates``/``weightDecays``); ``clip`` (a
+    GradClip whose Σg² buffer is filled) clips ``g·grad_scale`` first."""
     g = g.float()  # a bf16-wire gradient shard is consumed directly
     gg = g * grad_scale if grad_scale != 1.0 else g.clone()
+    if clip is not None:
+        clip.apply(gg, grad_scale)
     if weight_decay != 0:
         gg.add_(w * (wds if wds is not None else 1.0), alpha=weight_decay)
     if momentum != 0:
@@ -652,9 +655,11 @@ def sgd_step(w, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_s
     return w
 
 
-def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None):
+def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_scale=1.0, shadow=None, clip=None):
     """``DL/optim/Adam.scala``: bias-corrected Adam."""
     gg = g.float() * grad_scale  # a bf16-wire gradient shard is consumed directly
+    if clip is not None:
+        clip.apply(gg, grad_scale)
     if weight_decay != 0:
         gg = gg + weight_decay * w
     m.mul_(beta1).add_(gg, alpha=1 - beta1)
@@ -666,6 +671,13 @@ def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, weight_decay=0.0, grad_sc
     if shadow is not None:
         shadow.copy_(w)
     return w
+
+
+def grad_sumsq(g, out=None, partials=None):
+    """Σg² of a flat gradient as fp32 ``[1]`` (``out`` when given); ``g`` is fp32 or the bf16 wire
+    shard.  Accumulated in fp64, so the result is the rounded exact sum; no host read."""
+    r = g.double().square().sum().float().reshape(1)
+    return r if out is None else out.copy_(r)
 
 
 def lars_sumsq(w, g, table, sums=None):

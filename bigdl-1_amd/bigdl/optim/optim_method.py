@@ -27,6 +27,7 @@ from ..utils.table import Table
 
 class OptimMethod:
     SCALA_PACKAGE = "com.intel.analytics.bigdl.optim"
+    grad_clip = None  # methods restored from before the attribute existed
 
     def __init__(self):
         self.state = {"epoch": 1, "neval": 1, "evalCounter": 0}
@@ -34,6 +35,10 @@ class OptimMethod:
         self.grad_scale = 1.0
         #: optional bf16 shadow of x written by the fused kernel
         self.shadow: Optional[torch.Tensor] = None
+        #: gradient clipping folded into the update (a bigdl.parameters.GradClip whose Σg² buffer
+        #: the optimizer filled for this step), set by the optimizer next to grad_scale; None = the
+        #: gradient arrives already clipped, or unclipped
+        self.grad_clip = None
 
     def optimize(self, feval: Callable, x: torch.Tensor):
         raise NotImplementedError
@@ -414,7 +419,7 @@ class SGD(OptimMethod):
         buf = self.state["dfdx"][lo:hi] if self.momentum != 0 else None
         lrs, wd, wds = self._decays(x.device, lo, hi)
         ops.sgd_step(x[lo:hi], g[lo:hi], buf, -clr, self.momentum, self.dampening, wd, self.nesterov, self._first,
-                     self.grad_scale, shadow, lrs, wds)
+                     self.grad_scale, shadow, lrs, wds, clip=self.grad_clip)
 
     def optimize(self, feval, x):
         self.updateHyperParameter()
@@ -435,7 +440,7 @@ class SGD(OptimMethod):
             if not isinstance(fdev, torch.Tensor) or fdev.device != x.device:
                 fdev = self.state["_dev_first"] = torch.zeros(1, device=x.device)
         ops.sgd_step(x, dfdx, buf, -clr, self.momentum, self.dampening, wd, self.nesterov, first,
-                     self.grad_scale, self.shadow, lrs, wds, first_dev=fdev)
+                     self.grad_scale, self.shadow, lrs, wds, first_dev=fdev, clip=self.grad_clip)
         if fdev is not None:
             fdev.zero_()
         return x, [fx]
@@ -444,6 +449,7 @@ class SGD(OptimMethod):
         d = dict(self.__dict__)
         for k in ("_reg_decay", "_space_wds", "_space_lrs", "_eff_cache"):
             d.pop(k, None)
+        d["grad_clip"] = None  # the optimizer's, with device buffers: set again every step
         return d
 
 
@@ -484,9 +490,22 @@ class _Elementwise(OptimMethod):
     def _torch(self, x, g, sl):  # g = g.float() * grad_scale
         raise NotImplementedError
 
+    #: the wrapper ``_native`` launches and whether ``bigdl.optim.fused`` gates it
+    _op: Optional[str] = None
+    _gated = True
+
+    def takes_kernel(self, x) -> bool:
+        """True when the update of ``x`` goes to this method's rule kernel."""
+        return self._op is not None and _kernel(x, self._op, self._gated)
+
+    def _clipped(self, g):
+        """``g.float() * grad_scale`` for the torch form, clipped when the update carries the clip."""
+        g = g.float() * self.grad_scale
+        return g if self.grad_clip is None else self.grad_clip.apply(g, self.grad_scale)
+
     def _update(self, x, g, sl, shadow):
         if self._native(x, g, sl, shadow) is NotImplemented:
-            self._torch(x, g.float() * self.grad_scale, sl)
+            self._torch(x, self._clipped(g), sl)
             _write_shadow(shadow, x)
 
     def begin_iteration(self, x):
@@ -521,6 +540,8 @@ class Adam(_Elementwise):
         n = self.state.get("evalCounter", 0)
         return self.learningRate / (1 + n * self.learningRateDecay)
 
+    _op, _gated = "adam_step", False
+
     def _begin(self, x):
         n = self.state.get("evalCounter", 0)
         self._clr = self.learningRate / (1 + n * self.learningRateDecay)
@@ -532,7 +553,7 @@ class Adam(_Elementwise):
         # the dispatcher takes every operand: the kernel on the device, reference.adam_step (the
         # torch form, shadow included) on the CPU or when the kernel refuses
         return ops.adam_step(x, g, self.state["s"][sl], self.state["r"][sl], self._clr, self.beta1, self.beta2,
-                             self.epsilon, self._t, 0.0, self.grad_scale, shadow)
+                             self.epsilon, self._t, 0.0, self.grad_scale, shadow, clip=self.grad_clip)
 
     def optimize(self, feval, x):
         if not (getattr(self, "_graph_mode", False) and x.is_cuda):
@@ -541,7 +562,8 @@ class Adam(_Elementwise):
         fx, g = feval(x)
         m, v, nt = self._state_tensor("s", x), self._state_tensor("r", x), self._device_counter(x)
         r = ops.native_ops.adam_step_dev(x, g, m, v, nt, self.learningRate, self.learningRateDecay, self.beta1,
-                                         self.beta2, self.epsilon, 0.0, self.grad_scale, self.shadow)
+                                         self.beta2, self.epsilon, 0.0, self.grad_scale, self.shadow,
+                                         clip=self.grad_clip)
         if r is NotImplemented:
             raise NotImplementedError("Adam graph mode needs the native fused kernel")
         nt.add_(1)
@@ -569,6 +591,8 @@ class Adamax(_Elementwise):
         super().__init__()
         self.learningRate, self.beta1, self.beta2, self.epsilon = learningrate, beta1, beta2, epsilon
 
+    _op = "adamax_step"
+
     def _begin(self, x):
         self._t = self.state.get("evalCounter", 0) + 1
         self._state_tensor("m", x)
@@ -578,7 +602,8 @@ class Adamax(_Elementwise):
         if not _kernel(x, "adamax_step"):
             return NotImplemented
         return ops.native_ops.adamax_step(x, g, self.state["m"][sl], self.state["u"][sl], self.learningRate,
-                                          self.beta1, self.beta2, self.epsilon, self._t, self.grad_scale, shadow)
+                                          self.beta1, self.beta2, self.epsilon, self._t, self.grad_scale, shadow,
+                                          clip=self.grad_clip)
 
     def _torch(self, x, g, sl):
         m, u = self.state["m"][sl], self.state["u"][sl]
@@ -592,6 +617,8 @@ class Adagrad(_Elementwise):
         super().__init__()
         self.learningRate, self.learningRateDecay, self.weightDecay = learningrate, learningrate_decay, weightdecay
 
+    _op, _gated = "adagrad_step", False
+
     def _begin(self, x):
         self._n = self.state.get("evalCounter", 0)
         self._state_tensor("paramVariance", x)
@@ -601,7 +628,7 @@ class Adagrad(_Elementwise):
             return NotImplemented
         return ops.native_ops.adagrad_step(x, g, self.state["paramVariance"][sl], self.learningRate,
                                            self.learningRateDecay, self._n, self.weightDecay, self.grad_scale, shadow,
-                                           dev_n=dev_n)
+                                           dev_n=dev_n, clip=self.grad_clip)
 
     def _torch(self, x, g, sl, dev_n=None):
         s = self.state["paramVariance"][sl]
@@ -623,7 +650,7 @@ class Adagrad(_Elementwise):
         self._begin(x)
         nt, sl = self._device_counter(x), slice(0, x.numel())
         if self._native(x, g, sl, self.shadow, dev_n=nt) is NotImplemented:
-            self._torch(x, g.float() * self.grad_scale, sl, dev_n=nt)
+            self._torch(x, self._clipped(g), sl, dev_n=nt)
             _write_shadow(self.shadow, x)
         nt.add_(1)
         self.state["evalCounter"] = self._n + 1
@@ -639,6 +666,8 @@ class Adadelta(_Elementwise):
         super().__init__()
         self.decayRate, self.epsilon = decayrate, epsilon
 
+    _op = "adadelta_step"
+
     def _begin(self, x):
         self._state_tensor("paramVariance", x)
         self._state_tensor("delta", x)
@@ -647,7 +676,8 @@ class Adadelta(_Elementwise):
         if not _kernel(x, "adadelta_step"):
             return NotImplemented
         return ops.native_ops.adadelta_step(x, g, self.state["paramVariance"][sl], self.state["delta"][sl],
-                                            self.decayRate, self.epsilon, self.grad_scale, shadow)
+                                            self.decayRate, self.epsilon, self.grad_scale, shadow,
+                                            clip=self.grad_clip)
 
     def _torch(self, x, g, sl):
         v, d = self.state["paramVariance"][sl], self.state["delta"][sl]
@@ -663,6 +693,8 @@ class RMSprop(_Elementwise):
         self.learningRate, self.learningRateDecay = learningrate, learningrate_decay
         self.decayRate, self.epsilon = decayrate, epsilon
 
+    _op = "rmsprop_step"
+
     def _begin(self, x):
         n = self.state.get("evalCounter", 0)
         self._clr = self.learningRate / (1 + n * self.learningRateDecay)
@@ -672,7 +704,7 @@ class RMSprop(_Elementwise):
         if not _kernel(x, "rmsprop_step"):
             return NotImplemented
         return ops.native_ops.rmsprop_step(x, g, self.state["sumSquare"][sl], self._clr, self.decayRate, self.epsilon,
-                                           self.grad_scale, shadow)
+                                           self.grad_scale, shadow, clip=self.grad_clip)
 
     def _torch(self, x, g, sl):
         s = self.state["sumSquare"][sl]
@@ -692,6 +724,8 @@ class Ftrl(_Elementwise):
         self.l1, self.l2, self.l2Shrinkage = (l1_regularization_strength, l2_regularization_strength,
                                               l2_shrinkage_regularization_strength)
 
+    _op = "ftrl_step"
+
     def _begin(self, x):
         acc = self.state.get("accum")
         if not isinstance(acc, torch.Tensor) or acc.shape != x.shape or acc.device != x.device:
@@ -703,7 +737,7 @@ class Ftrl(_Elementwise):
             return NotImplemented
         return ops.native_ops.ftrl_step(x, g, self.state["accum"][sl], self.state["linear"][sl], self.learningRate,
                                         self.learningRatePower, self.l1, self.l2, self.l2Shrinkage, self.grad_scale,
-                                        shadow)
+                                        shadow, clip=self.grad_clip)
 
     def _torch(self, x, g, sl):
         acc, lin = self.state["accum"][sl], self.state["linear"][sl]

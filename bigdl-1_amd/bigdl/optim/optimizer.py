@@ -361,7 +361,14 @@ class BaseOptimizer:
         """Gradient aggregation + clipping + optimizer update (local: no aggregation)."""
         from ..ops import native_ops as NO
         NO.join_wgrad()  # weight gradients computed on the side stream
-        self._clip(self.flat.grad, self.flat.grad)
+        clip = self._fused_clip(self.flat.weight)
+        if clip is None:
+            self._clip(self.flat.grad, self.flat.grad)
+        else:
+            # one Σg² pass (L2 threshold only); the update kernels clip the gradient as they load it
+            clip.collect(self.flat.grad)
+        for meth in self.optim_methods.values():
+            meth.grad_clip = clip
         plan = getattr(self, "_lars_plan", None)
         with self.tracer.phase("compute weight"):
             if plan is not None:
@@ -389,6 +396,33 @@ class BaseOptimizer:
         if self.l2_clip is not None:
             procs.append(L2NormClippingProcessor(self.l2_clip))
         return procs
+
+    def _fused_clip(self, weight: torch.Tensor):
+        """The :class:`bigdl.parameters.GradClip` the update kernels take this step, or None when no
+        clipping is set or the processors must run (``_clip``): the one place that decides.  Fused
+        when the weights are on the device, ``bigdl.clip.fused`` is on, the kernels are loaded,
+        every method is SGD or an elementwise method that takes its rule kernel, and no LarsPlan is
+        present (its layer norms would have to be those of the clipped gradient)."""
+        if self.constant_clip is None and self.l2_clip is None:
+            return None
+        from . import optim_method as OM
+        from .. import ops
+        if not (weight.is_cuda and config.get_property("bigdl.clip.fused") and ops.native_has("grad_sumsq")
+                and getattr(self, "_lars_plan", None) is None):
+            return None
+        for m in self.optim_methods.values():
+            if isinstance(m, OM.LarsSGD):
+                return None
+            if isinstance(m, OM.SGD):
+                if not ops.native_has("sgd_step"):
+                    return None
+            elif not (isinstance(m, OM._Elementwise) and m.takes_kernel(weight)):
+                return None
+        key = (self.constant_clip, self.l2_clip)
+        if getattr(self, "_grad_clip_key", None) != key:
+            from ..parameters import GradClip
+            self._grad_clip, self._grad_clip_key = GradClip.of(self.constant_clip, self.l2_clip), key
+        return self._grad_clip
 
     def _clip(self, grad: torch.Tensor, local_shard: torch.Tensor):
         from ..parameters import run_processors

@@ -399,18 +399,23 @@ class DistriOptimizer(BaseOptimizer):
         # sent during backward
         self._overlap_active = (self.overlap and not self._first_iter and self._overlap_ok
                                 and not self._drop_mode())
-        # early (in-backward) shard updates: sharded, no clipping (which needs the global gradient
-        # norm before any update)
+        # early (in-backward) shard updates: sharded, no L2 clipping (which needs the global gradient
+        # norm before any update); a constant clamp needs nothing global, so it stays early when the
+        # update kernels apply it themselves
         # ... and no LarsPlan (its layer norms need every bucket's reduced gradient)
-        self._early = (self._overlap_active and self._early_ok
-                       and self.constant_clip is None and self.l2_clip is None
+        self._early = (self._overlap_active and self._early_ok and self.l2_clip is None
                        and getattr(self, "_lars_plan", None) is None)
+        early_clip = None
+        if self._early and self.constant_clip is not None:
+            early_clip = self._fused_clip(self.shard_w)
+            self._early = early_clip is not None
         if self._drop_mode():
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             self._t_compute0 = time.perf_counter()
         if self._early:
             for meth in self.optim_methods.values():
+                meth.grad_clip = early_clip
                 meth.begin_iteration(self.shard_w)
         self._hook_counts = {}
 
@@ -525,8 +530,20 @@ class DistriOptimizer(BaseOptimizer):
             return
         for meth in self.optim_methods.values():
             meth.grad_scale = 1.0 / fin
-        # sharded: clipping needs the global gradient norm before any update
+        # sharded: clipping needs the global gradient norm before any update.  Fused (GradClip): one
+        # Σg² pass over the reduced shard as it lies (the bf16 wire shard, or fp32), one all-reduced
+        # float, and the update kernels clip as they load, with grad_scale = 1/fin as without
+        # clipping: no unpack, no scaling pass, no clamp pass
         clipping = self.constant_clip is not None or self.l2_clip is not None
+        fused = self._fused_clip(self.shard_w) if clipping else None
+        for meth in self.optim_methods.values():
+            meth.grad_clip = fused
+        if fused is not None:
+            clipping = False
+            if fused.threshold is not None:
+                for b in self.buckets:
+                    self._finish_reduce(b)
+                fused.collect(self.shard_g_wire if self.grad_wire is not None else self.shard_g, self._global_sum)
         if clipping:
             for b in self.buckets:
                 self._finish_reduce(b, unpack=True)

@@ -25,7 +25,7 @@ from . import bigdl_pb as pb
 from .module_serializer import (_SerCtx, _DeCtx, _set_attr, _get_attr, _storage_from_pb, save_module, load_module,
                                 fill_global_storage, module_snapshot, module_snapshot_bytes)
 
-_SKIP = {"state", "shadow", "grad_scale", "slices", "_first", "_clr", "_t"}
+_SKIP = {"state", "shadow", "grad_scale", "grad_clip", "slices", "_first", "_clr", "_t"}
 
 
 def optim_to_pb(method, defer: bool = False):

@@ -81,6 +81,7 @@ _REGISTRY = {
     "bigdl.optim.foldRegularizers": (bool, True, "apply pure-L2 layer regularizers inside the fused SGD update"),
     "bigdl.lars.fused": (bool, True, "LarsSGD methods with device weights run as one LarsPlan (layer-norm kernels + one fused update, no host sync) under the LocalOptimizer and in replicated mode; sharded mode always uses the plan"),
     "bigdl.optim.fused": (bool, True, "Adamax, Adadelta, RMSprop and Ftrl update device weights in one fused HIP pass (csrc/optim_rules.hip) over the weights, gradient, state and bf16 shadow; false runs their torch elementwise form on the GPU too (A/B arm and escape hatch)"),
+    "bigdl.clip.fused": (bool, True, "gradient clipping (setConstantGradientClipping / setGradientClippingByl2Norm) of device weights runs inside the update kernels: one deterministic sum-of-squares pass over the gradient (csrc/clip.hip; the bf16 wire shard is read as it lies), one all-reduced float, and the clamp and the L2 scale applied as each kernel loads the gradient; false runs the parameter processors' torch passes over the gradient first (A/B arm and escape hatch).  LarsSGD and CPU weights always take the processors"),
     # fusion flags (bigdl.mkldnn.fusion.* equivalents, nn/mkldnn/Fusion.scala:34)
     "bigdl.int8.calibration": (str, "p99.999", "static int8 activation scale rule of quantize() after calcScales: max (max|x|, the reference's) or p99.9 / p99.99 / p99.999 (that percentile of |x|)"),
     "bigdl.int8.unsignedActivations": (bool, True, "a quantised conv whose ReLU is fused writes its non-negative int8 output as unsigned 8-bit (offset -128, scale clip/255); the consumer corrects the offset with per-tap weight sums"),

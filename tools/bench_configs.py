@@ -302,7 +302,10 @@ def bench_inception_train(args):
     (ClassNLLCriterion; SGD lr 0.01, momentum 0.9, dampening 0, no nesterov, weight decay 1e-4,
     Poly(0.5, 62000)), synthetic 224² data, batch 256, one GPU.  A/B of ``bigdl.concat.train`` (native
     concat in training, K19): two optimizers on identical models in one process, the arms alternated
-    ``--repeats`` times; the headline value is the property's default arm."""
+    ``--repeats`` times; the headline value is the property's default arm.  With ``--clip-l2 X`` both
+    optimizers clip the gradient to the L2 norm X (``--gradientL2NormThreshold`` of the reference's
+    recipe) and the A/B is ``bigdl.clip.fused`` instead: the clip inside the update kernel against
+    the parameter processors."""
     import copy
     import statistics
     import torch
@@ -325,7 +328,8 @@ def bench_inception_train(args):
     x = torch.randn(B, 3, 224, 224, generator=g).to(dev).to(dt).contiguous(memory_format=torch.channels_last)
     y = (torch.randint(0, 1000, (B,), generator=g) + 1).float().to(dev)
     batch = MiniBatch(x, y)
-    default_on = bool(config.get_property("bigdl.concat.train"))
+    prop = "bigdl.clip.fused" if args.clip_l2 > 0 else "bigdl.concat.train"
+    default_on = bool(config.get_property(prop))
     arms = [a for a in ("on", "off") if args.arm in ("both", a)]
     src = Inception_v1_NoAuxClassifier(1000)
     opts = {}
@@ -333,10 +337,12 @@ def bench_inception_train(args):
         sgd = SGD(learningrate=0.01, learningrate_decay=0.0, weightdecay=1e-4, momentum=0.9, dampening=0.0,
                   nesterov=False, leaningrate_schedule=Poly(0.5, 62000))
         opts[arm] = LocalOptimizer(copy.deepcopy(src), [batch], ClassNLLCriterion(), sgd, batch_size=B)
+        if args.clip_l2 > 0:
+            opts[arm].setGradientClippingByl2Norm(args.clip_l2)
         opts[arm].prepare()
 
     def run(arm, steps, warmup):
-        config.set_property("bigdl.concat.train", arm == "on")
+        config.set_property(prop, arm == "on")
         return _time_steps(lambda: opts[arm].train_step(batch), dev, steps, warmup)
 
     ms = {a: [] for a in arms}
@@ -351,7 +357,7 @@ def bench_inception_train(args):
             el, l = run(a, args.steps, 1)
             ms[a].append(round(el / args.steps * 1e3, 3))
             loss[a] = float(l)
-    config.set_property("bigdl.concat.train", default_on)
+    config.set_property(prop, default_on)
     head = ("on" if default_on else "off") if args.arm == "both" else arms[0]
     med = {a: statistics.median(v) for a, v in ms.items()}
     return {"metric": "images/sec Inception-v1 (NoAux) training 1 GPU", "value": round(B / med[head] * 1e3, 1),
@@ -359,6 +365,7 @@ def bench_inception_train(args):
             "ms_per_step": med[head], "higher_is_better": True, "dtype": args.dtype, "data": "synthetic",
             "config": {"model": "Inception_v1_NoAuxClassifier", "global_batch": B, "image_size": 224,
                        "optimizer": "SGD lr 0.01 momentum 0.9 wd 1e-4 Poly(0.5, 62000)", "headline_arm": head},
+            "ab_property": prop, "clip_l2": args.clip_l2 or None,
             "concat_train_ms_per_step": ms, "concat_train_median_ms": med,
             "on_over_off_speedup": round(med["off"] / med["on"], 4) if len(arms) == 2 else None,
             "reference_records_per_sec_16_nodes": 920, "final_loss": loss, "torch_fallbacks": fb}
@@ -635,6 +642,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="inception_train: timed runs per arm, arms alternated")
     ap.add_argument("--arm", default="both", choices=["both", "on", "off"],
                     help="inception_train: bigdl.concat.train arms to run (one arm: a profiling run)")
+    ap.add_argument("--clip-l2", type=float, default=0.0,
+                    help="inception_train: clip the gradient to this L2 norm and A/B bigdl.clip.fused (0 = off)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=0, help="0 = the config's reference default")
