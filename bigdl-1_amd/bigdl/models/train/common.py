@@ -78,18 +78,25 @@ def synthetic_images(n: int, h: int, w: int, c: int, classes: int, seed: int):
 
 
 def image_loader(images, labels, batch, crop, train, mean, std, args, pad=0, flip=None, layout=None):
-    """The native C++ batch loader (pinned slots, async H2D, per-rank partition)."""
+    """The native C++ batch loader (pinned slots, async H2D, per-rank partition).  ``--deviceAugment``
+    (implied by ``--alterAspect``) makes it a raw loader: uint8 pixels go up and one kernel crops, resizes,
+    mirrors, normalises and casts; ``--alterAspect`` draws the ``RandomAlterAspect`` rectangle for the
+    train split (the validation split gets the raw centre crop)."""
     from ...runtime.loader import NativeBatchLoader
     from ...utils.engine import Engine
     dev = Engine.device()
     on_gpu = dev.type == "cuda"
+    alter = bool(getattr(args, "alterAspect", False))
+    extra = {}
+    if alter or getattr(args, "deviceAugment", False):
+        extra = dict(raw=True, alter_aspect=(0.08, 1.0, 0.75) if (alter and train) else None, interp="CUBIC")
     return NativeBatchLoader(images, labels, batch, crop=crop, pad=pad, flip=train if flip is None else flip,
                              train=train, mean=mean, std=std,
                              dtype=torch.bfloat16 if (on_gpu and Engine.compute_dtype() == torch.bfloat16)
                              else torch.float32,
                              layout=layout or ("NHWC" if on_gpu else "NCHW"), shuffle=train, drop_last=train,
                              seed=args.seed, threads=args.threads, device=dev, rank=Engine.rank(),
-                             world=Engine.world_size())
+                             world=Engine.world_size(), **extra)
 
 
 def load_model_or(args, build):

@@ -9,6 +9,12 @@ partition).  ResNet: SGD with ``EpochDecayWithWarmUp`` (linear warm-up over ``--
 epochs from ``--learningRate`` to ``--maxLr``, then ×0.1 at epochs 30/60/80), optional SyncBN
 (``--syncBN``; the reference's ``setParallism``), Top-1/Top-5 validation and a checkpoint every
 epoch, Train/Validation summaries.
+
+``--deviceAugment`` sends the uint8 pixels up and runs crop, mirror, normalise and cast as one kernel on
+the loader's stream; ``--alterAspect`` (implies it) adds the reference's ``RandomAlterAspect`` for the
+train split.  With both, the ResNet CLI runs the reference's recipe (``models/resnet/DataSet.scala``
+``trainDataSet``): random-area (8–100 %), random-aspect (3/4–4/3) crop, resized to ``--imageSize``² with
+cubic interpolation, mirrored, then normalised.  Both are off by default.
 """
 from __future__ import annotations
 
@@ -38,6 +44,11 @@ def _parser():
     ap.add_argument("--maxLr", type=float, default=None)
     ap.add_argument("--syncBN", action="store_true", help="cross-rank BatchNorm statistics (setParallism)")
     ap.add_argument("--imageSize", type=int, default=224)
+    ap.add_argument("--deviceAugment", action="store_true",
+                    help="upload uint8 pixels; crop / mirror / normalise / cast in one kernel on the device")
+    ap.add_argument("--alterAspect", action="store_true",
+                    help="RandomAlterAspect (random area and aspect, cubic resize) for the train split; "
+                         "implies --deviceAugment")
     ap.add_argument("--test", action="store_true", help="TestImageNet: evaluate --model on the val set")
     return ap
 

@@ -11,6 +11,7 @@ static const char* kOps[] = {
     "concat_fwd", "concat_split_bwd", "sum_n",
     "rmsprop", "adadelta", "adamax", "ftrl", "adam_g16",
     "grad_sumsq", "sgd_clip", "optim_clip",
+    "image_resample_norm",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

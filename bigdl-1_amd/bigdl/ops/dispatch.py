@@ -18,7 +18,7 @@ __all__ = [
     "embedding_forward", "embedding_backward", "dropout_forward", "dropout_backward", "lrn_forward", "lrn_backward",
     "quant_rows", "gemm_i8", "image_crop_flip_norm", "attention_forward", "attention_backward",
     "attention_decode", "lars_sumsq", "lars_step", "grad_sumsq",
-    "concat_forward", "concat_split_backward", "sum_n",
+    "concat_forward", "concat_split_backward", "sum_n", "image_resample_norm",
 ]
 
 

@@ -2467,6 +2467,69 @@ def image_crop_flip_norm(src, oy, ox, flip, out_h, out_w, mean, std, to_rgb, out
     return out
 
 
+# ------------------------------------------------------------------------------------------------ image (K25b)
+_AUG_VARIANTS = {None: 0, "": 0, "auto": 0, "staged": 1, "direct": 2}
+_AUG_LAST = [0]
+
+
+def image_resample_last_variant() -> str:
+    """The kernel variant of the last ``image_resample_norm`` launch (``staged`` / ``direct``)."""
+    return {1: "staged", 2: "direct"}.get(_AUG_LAST[0], "")
+
+
+@register("image_resample_norm")
+def image_resample_norm(src, rects, flip, out_h, out_w, mean, std, to_rgb, interp="CUBIC", out_dtype=torch.float32,
+                        sizes=None, offsets=None, out=None, variant=None):
+    """``variant``: ``None`` (the host picks by the widest rectangle; ``BIGDL_IMAGE_AUG_VARIANT`` overrides),
+    ``"staged"`` or ``"direct"`` — for tests and the benchmark."""
+    import os
+    if src.dtype not in (torch.uint8, _f32) or not src.is_contiguous() or src.dim() not in (1, 4):
+        return NotImplemented
+    if out_dtype not in (_f32, _bf16) or interp not in R_._RESAMPLE_MODES or out_h <= 0 or out_w <= 0:
+        return NotImplemented
+    if (src.dim() == 4) != (sizes is None) or (src.dim() == 4 and src.shape[3] > 4):
+        return NotImplemented
+    tab, Cc = R_.resample_table(src, rects, flip, sizes, offsets)  # ValueError for a rectangle outside its image
+    if Cc > 4:
+        return NotImplemented
+    if variant is None:
+        variant = os.environ.get("BIGDL_IMAGE_AUG_VARIANT") or None
+    if variant not in _AUG_VARIANTS:
+        raise ValueError(f"variant must be staged or direct, not {variant!r}")
+    desc = torch.from_numpy(tab).pin_memory().to(src.device, non_blocking=True)
+    return image_resample_launch(src, desc, tab.shape[0], Cc, int(tab[:, 5].max()), int(tab[:, 6].max()), out_h,
+                                 out_w, mean, std, to_rgb, interp, out_dtype, out, variant)
+
+
+def image_resample_launch(src, desc, B, Cc, max_ch, max_cw, out_h, out_w, mean, std, to_rgb, interp, out_dtype,
+                          out=None, variant=None):
+    """Launch K25b on the current stream with a descriptor table that already sits on the device (``desc``
+    int64 [B, 8]; the caller has checked its rows on the host — :func:`reference.resample_table`).
+    ``max_ch`` / ``max_cw``: the tallest / widest rectangle of the batch."""
+    dev = src.device
+    if out is None:
+        out = torch.empty((B, Cc, out_h, out_w), dtype=out_dtype, device=dev, memory_format=torch.channels_last)
+    elif (tuple(out.shape) != (B, Cc, out_h, out_w) or out.dtype != out_dtype or out.device != dev
+          or not out.permute(0, 2, 3, 1).is_contiguous()):
+        raise ValueError("out must be a channels-last [B, C, OH, OW] tensor of out_dtype on the source's device")
+    if desc.dtype != torch.int64 or desc.device != dev or not desc.is_contiguous() or desc.numel() < B * 8:
+        raise ValueError("descriptor table must be a contiguous int64 [B, 8] tensor on the source's device")
+    mean_f = (C.c_float * 4)(*[float(v) for v in list(mean)[:Cc]])
+    std_f = (C.c_float * 4)(*[float(v) for v in list(std)[:Cc]])
+    got = C.c_int(0)
+    rc = _lib().bigdl_image_resample_norm(
+        ptr(src), C.c_longlong(src.numel() * src.element_size()), C.c_int(1 if src.dtype == torch.uint8 else 0),
+        ptr(desc), C.c_int(B), C.c_int(Cc), C.c_int(max_ch), C.c_int(max_cw),
+        C.c_int(out_h), C.c_int(out_w), mean_f, std_f, C.c_int(1 if to_rgb else 0),
+        C.c_int(R_._RESAMPLE_MODES[interp][1]), ptr(out), C.c_int(1 if out_dtype == _bf16 else 0),
+        C.c_int(_AUG_VARIANTS[variant]), C.byref(got), _s())
+    if rc != 0 and variant == "staged":
+        raise ValueError("the staged variant does not fit its LDS budget for this batch")
+    check(rc, "image_resample_norm")
+    _AUG_LAST[0] = got.value
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ pooling (K10)
 def _pool_out(size, k, s, p, ceil_mode):
     if ceil_mode:

@@ -867,6 +867,93 @@ def image_crop_flip_norm(src, oy, ox, flip, out_h, out_w, mean, std, to_rgb, out
     return t.permute(0, 3, 1, 2).to(out_dtype)
 
 
+_RESAMPLE_MODES = {"LINEAR": ("bilinear", 1), "CUBIC": ("bicubic", 2)}
+
+
+def resample_table(src, rects, flip, sizes=None, offsets=None):
+    """Host checks and descriptor table of :func:`image_resample_norm`: int64 rows
+    ``{byte offset, H, W, y0, x0, ch, cw, flip}`` (a numpy array) and the channel count.
+    Dense ``src [B, H, W, C]``: offsets are filled in.  Packed 1-D ``src``: ``sizes [B, 3]`` holds
+    (H, W, C) per image (one C for the batch) and ``offsets [B]`` byte offsets (default: back to back).
+    ``ValueError`` for an empty rectangle, one outside its image, or an image outside the buffer."""
+    import numpy as np
+    item = src.element_size()
+    rc = np.asarray(torch.as_tensor(rects).cpu(), dtype=np.int64).reshape(-1, 4)
+    B = rc.shape[0]
+    fl = np.asarray(torch.as_tensor(flip).cpu(), dtype=np.int64).reshape(-1)
+    if B == 0 or fl.shape[0] != B:
+        raise ValueError("rects [B, 4] and flip [B] must describe the same non-empty batch")
+    if sizes is None:
+        if src.dim() != 4 or src.shape[0] != B:
+            raise ValueError("dense source must be [B, H, W, C] with one rectangle per image")
+        _, H, W, Cc = src.shape
+        sz = np.tile(np.array([H, W, Cc], dtype=np.int64), (B, 1))
+        off = np.arange(B, dtype=np.int64) * (H * W * Cc * item)
+    else:
+        if src.dim() != 1:
+            raise ValueError("packed source must be a 1-D buffer")
+        sz = np.asarray(torch.as_tensor(sizes).cpu(), dtype=np.int64).reshape(-1, 3)
+        if sz.shape[0] != B or (sz[:, 2] != sz[0, 2]).any() or (sz <= 0).any():
+            raise ValueError("sizes must be [B, 3] positive (H, W, C) rows with one channel count")
+        nbytes = sz[:, 0] * sz[:, 1] * sz[:, 2] * item
+        if offsets is None:
+            off = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+        else:
+            off = np.asarray(torch.as_tensor(offsets).cpu(), dtype=np.int64).reshape(-1)
+            if off.shape[0] != B:
+                raise ValueError("offsets must be [B]")
+    Cc = int(sz[0, 2])
+    end = off + sz[:, 0] * sz[:, 1] * sz[:, 2] * item
+    if (off < 0).any() or (off % item != 0).any() or (end > src.numel() * item).any():
+        raise ValueError("image outside the source buffer")
+    y0, x0, ch, cw = rc[:, 0], rc[:, 1], rc[:, 2], rc[:, 3]
+    if (ch <= 0).any() or (cw <= 0).any() or (y0 < 0).any() or (x0 < 0).any() or \
+            (y0 + ch > sz[:, 0]).any() or (x0 + cw > sz[:, 1]).any():
+        raise ValueError("crop rectangle empty or outside the image")
+    tab = np.stack([off, sz[:, 0], sz[:, 1], y0, x0, ch, cw, (fl != 0).astype(np.int64)], axis=1)
+    return np.ascontiguousarray(tab, dtype=np.int64), Cc
+
+
+def image_resample_norm(src, rects, flip, out_h, out_w, mean, std, to_rgb, interp="CUBIC",
+                        out_dtype=torch.float32, sizes=None, offsets=None, out=None, variant=None):
+    """Batched crop → resize → mirror → per-channel (x − mean)/std (+ BGR→RGB) of HWC images (uint8 or
+    float) → NCHW-logical channels-last tensor of ``out_dtype``.  ``rects [B, 4]`` = (y0, x0, ch, cw); the
+    rectangle is resized to ``out_h × out_w`` as an image of its own (half-pixel centres, border taps
+    clamped to the rectangle; ``interp`` LINEAR or CUBIC with A = −0.75, CUBIC clamped to [0, 255]).
+    ``src`` is dense ``[B, H, W, C]`` or a packed 1-D buffer with ``sizes``/``offsets``
+    (:func:`resample_table`).  ``mean``/``std`` are given in OUTPUT channel order.  This is the fp32
+    torch form (``F.interpolate``); ``variant`` only concerns the HIP kernel."""
+    if interp not in _RESAMPLE_MODES:
+        raise ValueError(f"interp must be LINEAR or CUBIC, not {interp!r}")
+    tab, C = resample_table(src, rects, flip, sizes, offsets)
+    if C > 4:
+        raise ValueError("at most 4 channels")
+    mode = _RESAMPLE_MODES[interp][0]
+    flat = src.reshape(-1)
+    item = src.element_size()
+    outs = []
+    for off, H, W, y0, x0, ch, cw, fl in tab.tolist():
+        img = flat[off // item: off // item + H * W * C].reshape(H, W, C)
+        t = img[y0:y0 + ch, x0:x0 + cw].float().permute(2, 0, 1).unsqueeze(0)
+        t = F.interpolate(t, size=(int(out_h), int(out_w)), mode=mode, align_corners=False)
+        if mode == "bicubic":
+            t = t.clamp(0.0, 255.0)
+        t = t.squeeze(0).permute(1, 2, 0)
+        if fl:
+            t = t.flip(1)
+        if to_rgb and C == 3:
+            t = t.flip(2)
+        outs.append(t)
+    t = torch.stack(outs)
+    m = torch.tensor(list(mean)[:C], dtype=torch.float32, device=src.device)
+    s = torch.tensor(list(std)[:C], dtype=torch.float32, device=src.device)
+    t = ((t - m) / s).permute(0, 3, 1, 2).to(out_dtype)
+    if out is not None:
+        out.copy_(t)
+        return out
+    return t
+
+
 # ------------------------------------------------------------------------- attention (K30)
 _M32 = 0xFFFFFFFF
 

@@ -10,7 +10,16 @@
 // uses its own shuffled permutation (Fisher-Yates on mt19937_64(seed + epoch)), and sample i of
 // batch b draws its crop/flip from mt19937_64(seed ^ hash(b, i)) — results do not depend on the
 // thread count or timing.  The iterator is infinite (train mode of CachedDistriDataSet).
+//
+// Raw mode (bigdl_loader_create_raw): the workers only memcpy the batch's uint8 images into the slot and
+// write one descriptor row per image {byte offset in the slot, H, W, y0, x0, ch, cw, flip} (int64 × 8) into
+// a second slot block; crop, resize, mirror, normalise and cast then run on the device in one kernel
+// (ops/csrc/image_aug.hip).  The rectangle and the flip come from the same per-(batch, row) stream:
+// train with alter_aspect — the RandomAlterAspect rule (area ratio and aspect from randRatio, a swap coin,
+// at most ten attempts, then the whole image), then a flip coin; train without — the random fixed-size
+// crop and flip of the host mode; eval — the centred crop, no flip.
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -53,6 +62,10 @@ struct Loader {
   int64_t nb;  // batches per epoch
   std::vector<void*> slots_x;
   std::vector<float*> slots_y;
+  // raw mode
+  int raw = 0, alter = 0;
+  double min_area = 0.08, max_area = 1.0, min_aspect = 0.75;
+  std::vector<int64_t*> slots_desc;
   std::vector<int> state;
   std::vector<int64_t> slot_batch;
   std::vector<int> slot_rows;
@@ -128,6 +141,61 @@ struct Loader {
     slot_rows[slot] = rows;
   }
 
+  static double uniform(std::mt19937_64& g, double a, double b) {
+    return a + (double)(g() >> 11) * (1.0 / 9007199254740992.0) * (b - a);
+  }
+  // RandomAlterAspect.randRatio
+  static double rand_ratio(std::mt19937_64& g, double lo, double hi) {
+    return (uniform(g, 1e-2, (hi - lo) * 1000 + 1) + lo * 1000) / 1000;
+  }
+
+  void fill_raw(int slot, int64_t b) {
+    const int64_t epoch = b / nb, off = (b % nb) * batch;
+    const std::vector<int64_t>& p = permutation(epoch);
+    const int rows = (int)std::min<int64_t>(batch, n - off);
+    const size_t img_bytes = (size_t)h * w * c;
+    for (int r = 0; r < rows; ++r) {
+      const int64_t idx = p[off + r];
+      std::memcpy((uint8_t*)slots_x[slot] + (size_t)r * img_bytes, data + (size_t)idx * img_bytes, img_bytes);
+      std::mt19937_64 g64(mix(seed ^ mix((uint64_t)b * 1315423911ULL + (uint64_t)r)));
+      int y0, x0, rh = ch, rw = cw, fl = 0;
+      if (!train) {
+        y0 = (h - ch) / 2;
+        x0 = (w - cw) / 2;
+      } else if (alter) {
+        y0 = x0 = 0;
+        rh = h;
+        rw = w;
+        for (int attempt = 0; attempt < 10; ++attempt) {
+          const double ar = rand_ratio(g64, min_area, max_area);
+          const double asp = rand_ratio(g64, min_aspect, 1.0 / min_aspect);
+          const double side = std::sqrt(ar * h * w);
+          int nh = (int)(side * asp), nw = (int)(side / asp);
+          if (rand_ratio(g64, 0, 1) < 0.5) std::swap(nh, nw);
+          if (nh > 0 && nh <= h && nw > 0 && nw <= w) {
+            y0 = std::min((int)uniform(g64, 1e-2, h - nh + 1), h - nh);
+            x0 = std::min((int)uniform(g64, 1e-2, w - nw + 1), w - nw);
+            rh = nh;
+            rw = nw;
+            break;
+          }
+        }
+        fl = flip && (g64() & 1);
+      } else {
+        y0 = (int)(g64() % (uint64_t)(h - ch + 1));
+        x0 = (int)(g64() % (uint64_t)(w - cw + 1));
+        fl = flip && (g64() & 1);
+      }
+      int64_t* d = slots_desc[slot] + (size_t)r * 8;
+      d[0] = (int64_t)((size_t)r * img_bytes);
+      d[1] = h; d[2] = w; d[3] = y0; d[4] = x0; d[5] = rh; d[6] = rw; d[7] = fl;
+      if (labels)
+        std::memcpy(slots_y[slot] + (size_t)r * label_dim, labels + (size_t)idx * label_dim,
+                    sizeof(float) * label_dim);
+    }
+    slot_rows[slot] = rows;
+  }
+
   void worker() {
     const int K = (int)slots_x.size();
     for (;;) {
@@ -140,7 +208,10 @@ struct Loader {
         state[slot] = FILLING;
         slot_batch[slot] = b;
       }
-      fill(slot, b);
+      if (raw)
+        fill_raw(slot, b);
+      else
+        fill(slot, b);
       {
         std::lock_guard<std::mutex> lk(mu);
         state[slot] = READY;
@@ -179,6 +250,44 @@ EXPORT void* bigdl_loader_create(const uint8_t* data, const float* labels, long 
   for (int i = 0; i < k; ++i) {
     L->slots_x.push_back(slots_x[i]);
     L->slots_y.push_back(slots_y ? slots_y[i] : nullptr);
+  }
+  L->state.assign(k, FREE);
+  L->slot_batch.assign(k, -1);
+  L->slot_rows.assign(k, 0);
+  for (int t = 0; t < threads; ++t) L->workers.emplace_back([L] { L->worker(); });
+  return L;
+}
+
+// Raw mode: `slots_x[K]` hold batch·h·w·c uint8 pixels, `slots_desc[K]` batch·8 int64 descriptor rows.
+// `crop_h × crop_w` is the output size: the size of the rectangle, unless `alter` draws it.
+EXPORT void* bigdl_loader_create_raw(const uint8_t* data, const float* labels, long long n, int h, int w, int c,
+                                     int label_dim, int batch, int crop_h, int crop_w, int flip, int train,
+                                     int alter, double min_area, double max_area, double min_aspect, int shuffle,
+                                     int drop_last, unsigned long long seed, int threads, int k, void** slots_x,
+                                     float** slots_y, long long** slots_desc) {
+  if (!data || n <= 0 || h <= 0 || w <= 0 || c <= 0 || batch <= 0 || crop_h <= 0 || crop_w <= 0 || threads <= 0 ||
+      k < 1 || (labels && label_dim <= 0) || !slots_x || !slots_desc)
+    return nullptr;
+  const bool fixed = !(alter && train);  // a fixed-size rectangle has to fit the image
+  if (fixed && (crop_h > h || crop_w > w)) return nullptr;
+  if (alter && !(min_area > 0 && max_area >= min_area && min_aspect > 0 && min_aspect <= 1)) return nullptr;
+  if (drop_last && n < batch) return nullptr;
+  Loader* L = new Loader();
+  L->data = data;
+  L->labels = labels;
+  L->n = n;
+  L->h = h; L->w = w; L->c = c; L->label_dim = label_dim;
+  L->batch = batch; L->ch = crop_h; L->cw = crop_w; L->pad = 0; L->flip = flip; L->train = train;
+  L->bf16 = 0; L->nhwc = 1; L->shuffle = shuffle; L->drop_last = drop_last;
+  L->seed = seed;
+  L->nb = drop_last ? n / batch : (n + batch - 1) / batch;
+  L->raw = 1;
+  L->alter = alter;
+  L->min_area = min_area; L->max_area = max_area; L->min_aspect = min_aspect;
+  for (int i = 0; i < k; ++i) {
+    L->slots_x.push_back(slots_x[i]);
+    L->slots_y.push_back(slots_y ? slots_y[i] : nullptr);
+    L->slots_desc.push_back((int64_t*)slots_desc[i]);
   }
   L->state.assign(k, FREE);
   L->slot_batch.assign(k, -1);

@@ -287,17 +287,21 @@ class Crop(FeatureTransformer):
         raise NotImplementedError
 
     @staticmethod
-    def crop(f: ImageFeature, x1, y1, x2, y2, normalized: bool, is_clip: bool):
-        m = f.opencv_mat()
-        h, w = m.shape[0], m.shape[1]
+    def window(h: int, w: int, x1, y1, x2, y2, normalized: bool, is_clip: bool):
+        """The integer window ``(y, x, ch, cw)`` that :meth:`crop` slices from an ``h × w`` image."""
         if normalized:
             x1, x2 = x1 * w, x2 * w
             y1, y2 = y1 * h, y2 * h
         if is_clip:
             x1, x2 = max(0.0, min(x1, w)), max(0.0, min(x2, w))
             y1, y2 = max(0.0, min(y1, h)), max(0.0, min(y2, h))
-        xi1, yi1 = int(x1), int(y1)
-        cw, ch = max(1, int(x2 - x1)), max(1, int(y2 - y1))
+        return int(y1), int(x1), max(1, int(y2 - y1)), max(1, int(x2 - x1))
+
+    @staticmethod
+    def crop(f: ImageFeature, x1, y1, x2, y2, normalized: bool, is_clip: bool):
+        m = f.opencv_mat()
+        h, w = m.shape[0], m.shape[1]
+        yi1, xi1, ch, cw = Crop.window(h, w, x1, y1, x2, y2, normalized, is_clip)
         f.set_mat(m[yi1:yi1 + ch, xi1:xi1 + cw].contiguous())
         f[ImageFeature.cropBbox] = (xi1 / w, yi1 / h, (xi1 + cw) / w, (yi1 + ch) / h)
 
@@ -312,7 +316,9 @@ class CenterCrop(Crop):
         self.cw, self.ch = crop_width, crop_height
 
     def box(self, f):
-        h, w = f.get_height(), f.get_width()
+        return self.box_for(f.get_height(), f.get_width())
+
+    def box_for(self, h: int, w: int):
         x1 = (w - self.cw) / 2.0
         y1 = (h - self.ch) / 2.0
         return x1, y1, x1 + self.cw, y1 + self.ch
@@ -324,7 +330,9 @@ class RandomCrop(Crop):
         self.cw, self.ch = crop_width, crop_height
 
     def box(self, f):
-        h, w = f.get_height(), f.get_width()
+        return self.box_for(f.get_height(), f.get_width())
+
+    def box_for(self, h: int, w: int):
         x1 = math.floor(RNG.uniform(0, max(w - self.cw, 0) + 1e-9))
         y1 = math.floor(RNG.uniform(0, max(h - self.ch, 0) + 1e-9))
         x1 = min(x1, max(w - self.cw, 0))
@@ -363,16 +371,20 @@ class RandomCropper(FeatureTransformer):
         self.cw, self.ch, self.mirror, self.method, self.channels = crop_width, crop_height, mirror, \
             cropper_method, channels
 
-    def transform_mat(self, f):
-        m = f.opencv_mat()
-        h, w = m.shape[0], m.shape[1]
+    def draw(self, h: int, w: int):
+        """The crop origin and mirror coin for an ``h × w`` image → ``(y, x, flip)``."""
         if self.method.lower().startswith("random"):
             y = int(RNG.uniform(0, h - self.ch + 1)) if h > self.ch else 0
             x = int(RNG.uniform(0, w - self.cw + 1)) if w > self.cw else 0
         else:
             y, x = (h - self.ch) // 2, (w - self.cw) // 2
+        return y, x, bool(self.mirror and RNG.uniform(0, 1) < 0.5)
+
+    def transform_mat(self, f):
+        m = f.opencv_mat()
+        y, x, flip = self.draw(m.shape[0], m.shape[1])
         out = m[y:y + self.ch, x:x + self.cw]
-        if self.mirror and RNG.uniform(0, 1) < 0.5:
+        if flip:
             out = out.flip(1)
         f.set_mat(out[..., :self.channels].contiguous())
 
@@ -391,9 +403,9 @@ class RandomAlterAspect(FeatureTransformer):
     def _rand_ratio(lo, hi):
         return (RNG.uniform(1e-2, (hi - lo) * 1000 + 1) + lo * 1000) / 1000
 
-    def transform_mat(self, f):
-        m = f.opencv_mat()
-        h, w = m.shape[0], m.shape[1]
+    def draw(self, h: int, w: int):
+        """The rectangle of an ``h × w`` image that is resized to ``crop_length``² → ``(y, x, nh, nw)``;
+        the whole image after ten failed attempts."""
         for _ in range(10):
             ar = self._rand_ratio(self.min_area, self.max_area)
             asp = self._rand_ratio(self.min_ar, 1 / self.min_ar)
@@ -404,9 +416,13 @@ class RandomAlterAspect(FeatureTransformer):
             if 0 < nh <= h and 0 < nw <= w:
                 y = int(RNG.uniform(1e-2, h - nh + 1))
                 x = int(RNG.uniform(1e-2, w - nw + 1))
-                f.set_mat(resize_mat(m[y:y + nh, x:x + nw], self.L, self.L, self.mode))
-                return
-        f.set_mat(resize_mat(m, self.L, self.L, self.mode))
+                return y, x, nh, nw
+        return 0, 0, h, w
+
+    def transform_mat(self, f):
+        m = f.opencv_mat()
+        y, x, nh, nw = self.draw(m.shape[0], m.shape[1])
+        f.set_mat(resize_mat(m[y:y + nh, x:x + nw], self.L, self.L, self.mode))
 
 
 class Expand(FeatureTransformer):
