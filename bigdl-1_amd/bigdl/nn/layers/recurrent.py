@@ -16,7 +16,11 @@ Design (MI355X-first, not the reference's clone-a-cell-per-step scheme):
   the (B, T, H) output); BPTT runs per step one fused backward kernel plus one dgrad GEMM, and
   the recurrent weight gradient dU = Σ_t dgates_tᵀ·h_{t-1} is ONE (4H × B·T) · (B·T × H) GEMM
   after the loop instead of T small ones.
-* Every other cell (GRU, RnnCell, peephole, ConvLSTM, MultiRNNCell, custom cells) declares a
+* **RnnCell / LSTMPeephole fast paths** (``p == 0``, RnnCell with Tanh / ReLU / Sigmoid): the same
+  one-launch-per-step kernels (rnn_step.hip cells 6-9) with explicit BPTT; the peephole cell's four
+  ``h2g`` weights are read in place, its CMul gradients come from one column-reduction kernel.
+  ``bigdl.rnn.nativeCells=false`` sends these two cells back to the generic path.
+* Every other cell (GRU with dropout, ConvLSTM, MultiRNNCell, custom cells) declares a
   differentiable ``step(x, hidden, tape)`` on torch device ops; the time loop is recorded once
   and BPTT is a single autograd pass.  Parameters enter through a ``_Tape`` that hands out
   compute-dtype leaves, fires the owning modules' pre-forward hooks (the DistriOptimizer's
@@ -40,7 +44,7 @@ from .dropout import Dropout
 from .linear import Linear
 from .math_ops import CMul
 from .shape import Identity
-from ...utils import acc_float
+from ...utils import acc_float, config
 
 
 # ============================================================================ tape
@@ -164,6 +168,38 @@ def _acc_recurrent_grad(m, DG, h0, out, U):
         if m.wRegularizer is not None:
             m.wRegularizer.accRegularization(m.weight, m.gradWeight, m.scale_w)
     _fire_grad_ready([m])
+
+
+def _hprev_rows(h0, out):
+    """(h0, out[:, :-1]) as B·T rows: the step inputs of the recurrent weight gradient."""
+    B, Tn, H = out.shape
+    hprev = torch.cat([h0.unsqueeze(1), out[:, :-1]], 1) if Tn > 1 else h0.unsqueeze(1)
+    return hprev.reshape(B * Tn, H)
+
+
+def _acc_h2g_grad(m, dg, hprev, U):
+    """One h2g Linear of a native cell: gradWeight += Σ_t dg_tᵀ h_{t-1} (one GEMM over all B·T rows),
+    gradBias += Σ dg (column sum), with the module's scales and regularisers."""
+    if m.scale_w != 0:
+        ops.linear_backward(dg, hprev, U, False, m.gradWeight, None, m.scale_w)
+        if m.wRegularizer is not None:
+            m.wRegularizer.accRegularization(m.weight, m.gradWeight, m.scale_w)
+    if m.withBias and m.scale_b != 0:
+        from ...ops import native_ops as NO
+        if NO.colsum_acc(dg, m.gradBias, m.scale_b) is NotImplemented:
+            raise RuntimeError("recurrent h2h bias gradient: no native column sum for these rows")
+        reg = getattr(m, "bRegularizer", None)
+        if reg is not None:
+            reg.accRegularization(m.bias, m.gradBias, m.scale_b)
+
+
+def _native_cell_operands_ok(H, x2, *Us) -> bool:
+    """Operand contract of the RnnCell / LSTMPeephole step kernels: bf16 or fp32 device rows,
+    H % 8 == 0, dense 16-byte-aligned weights."""
+    if not (_fused_rnn_ok(H, x2, *Us) or _fused_rnn32_ok(H, x2, *Us)):
+        return False
+    from ...ops import native_ops as NO
+    return NO.rnn_dense_ok(*Us)
 
 
 def _fused_rnn32_ok(H, *ts) -> bool:
@@ -813,6 +849,25 @@ class Recurrent(Container):
         w1, w2 = c.h2g[0].cw("weight"), c.u_h.cw("weight")
         return _fused_rnn_ok(c.outputSize, x2, w1, w2) or _fused_rnn32_ok(c.outputSize, x2, w1, w2)
 
+    def _native_cells(self, x2):
+        return (self.fast_lstm and not self.maskZero and x2.dim() == 3
+                and bool(config.get_property("bigdl.rnn.nativeCells")))
+
+    def _use_fast_rnn(self, x2):
+        c = self.topology
+        if not (type(c) is RnnCell and self._native_cells(x2) and type(c.activation) in (Tanh, ReLU, Sigmoid)):
+            return False
+        gb = c.h2h.gradBias if c.h2h.withBias else None  # the native column sum adds into fp32 rows only
+        if gb is not None and not (gb.dtype == torch.float32 and gb.is_contiguous()):
+            return False
+        return _native_cell_operands_ok(c.hiddenSize, x2, c.h2h.cw("weight"))
+
+    def _use_fast_peephole(self, x2):
+        c = self.topology
+        if not (type(c) is LSTMPeephole and c.p == 0 and self._native_cells(x2)):
+            return False
+        return _native_cell_operands_ok(c.hiddenSize, x2, *[l.cw("weight") for l in c.h2g])
+
     # -- stacked-LSTM fusion (bigdl.nn.fusion ``lstmstack``) ----------------------------------
     #: lower layer: the next Recurrent(LSTM) whose only input is this layer's output; upper layer:
     #: the layer feeding it.  The pair then runs on the layer wavefront (rnn_step.hip
@@ -857,6 +912,10 @@ class Recurrent(Container):
             return self._lstm_forward(x2)
         if self._use_fast_gru(x2):
             return self._gru_forward(x2)
+        if self._use_fast_rnn(x2):
+            return self._rnn_forward(x2)
+        if self._use_fast_peephole(x2):
+            return self._lstmp_forward(x2)
         return self._generic_forward(input, x2)
 
     def _lstm_forward(self, x2):
@@ -983,6 +1042,57 @@ class Recurrent(Container):
         self._rec = ("gru", h0, out, R, Z, Nn, RH) if train else None
         return out
 
+    def _rnn_forward(self, x2):
+        """RnnCell time loop on one fused launch per step (rnn_step.hip cell 6)."""
+        from ...ops import native_ops as NO
+        cell: RnnCell = self.topology
+        B, Tn, H = x2.shape
+        h2h = cell.h2h
+        _fire_pre_forward([h2h])
+        U = h2h.cw("weight")
+        bh = h2h.bias.detach().to(torch.float32).contiguous() if h2h.withBias else None
+        (h0,) = self._h0(B, [H], x2.device, x2.dtype)
+        h0 = h0.to(x2.dtype).contiguous()
+        out = torch.empty(B, Tn, H, device=x2.device, dtype=x2.dtype)
+        train = self.train
+        hs = torch.empty(Tn, B, H, device=x2.device, dtype=torch.float32) if train else None
+        kind = type(cell.activation).__name__
+        fwd = NO.rnn_seq_forward32 if x2.dtype == torch.float32 else NO.rnn_seq_forward
+        fwd(x2.contiguous(), h0, bh, U, out, hs, kind)
+        self._last_hidden = out[:, Tn - 1]
+        self._rec = ("rnn", h0, out, hs, kind) if train else None
+        return out
+
+    def _lstmp_forward(self, x2):
+        """LSTMPeephole time loop on one fused launch per step (rnn_step.hip cell 8); the four h2g
+        weights are read where they lie."""
+        from ...ops import native_ops as NO
+        cell: LSTMPeephole = self.topology
+        B, Tn, G = x2.shape
+        H = cell.hiddenSize
+        _fire_pre_forward(cell.h2g + cell.peep)
+        Ug = [l.cw("weight") for l in cell.h2g]
+        peep = torch.stack([m.weight.detach().reshape(H).to(torch.float32) for m in cell.peep])
+        h0, c0 = self._h0(B, [H], x2.device, x2.dtype)
+        h0 = h0.to(x2.dtype).contiguous()
+        c0 = acc_float(c0).contiguous()
+        dev = x2.device
+        out = torch.empty(B, Tn, H, device=dev, dtype=x2.dtype)
+        train = self.train
+        if train:
+            acts = torch.empty(Tn, B, G, device=dev, dtype=torch.float32)
+            tcs = torch.empty(Tn, B, H, device=dev, dtype=torch.float32)
+            cs = torch.empty(Tn, B, H, device=dev, dtype=torch.float32)
+            cbuf = None
+        else:
+            acts = tcs = cs = None
+            cbuf = torch.empty(2, B, H, device=dev, dtype=torch.float32)
+        fwd = NO.lstmp_seq_forward32 if x2.dtype == torch.float32 else NO.lstmp_seq_forward
+        fwd(x2.contiguous(), h0, c0, Ug, peep, out, cs, acts, tcs, cbuf)
+        self._last_hidden = T(out[:, Tn - 1], cs[Tn - 1] if train else cbuf[(Tn - 1) % 2])
+        self._rec = ("lstmp", h0, c0, out, acts, tcs, cs, peep) if train else None
+        return out
+
     def _generic_forward(self, input, x2):
         cell = self.topology
         B, Tn = x2.shape[0], x2.shape[1]
@@ -1035,6 +1145,10 @@ class Recurrent(Container):
             return self._lstm2_backward(gradOutput)
         if rec[0] == "gru":
             return self._gru_backward(gradOutput)
+        if rec[0] == "rnn":
+            return self._rnn_backward(gradOutput)
+        if rec[0] == "lstmp":
+            return self._lstmp_backward(gradOutput)
         _, tape, xl, flat0, out = rec
         targets = ([xl] if xl.requires_grad else []) + flat0 + tape.param_leaves()
         grads = torch.autograd.grad([out], targets, [gradOutput.to(out.dtype)], allow_unused=True)
@@ -1143,6 +1257,69 @@ class Recurrent(Container):
             if uh.wRegularizer is not None:
                 uh.wRegularizer.accRegularization(uh.weight, uh.gradWeight, uh.scale_w)
         _fire_grad_ready([urz, uh])
+        self._rec = None
+        return DG
+
+    def _rnn_backward(self, gradOutput):
+        from ...ops import native_ops as NO
+        _, h0, out, hs, kind = self._rec
+        h2h = self.topology.h2h
+        U = h2h.cw("weight")
+        B, Tn, H = out.shape
+        gy = gradOutput.to(out.dtype)
+        if not gy.is_contiguous():
+            gy = gy.contiguous()
+        DG = torch.empty(B, Tn, H, device=out.device, dtype=out.dtype)  # da_t per step
+        if out.dtype == torch.float32:
+            NO.rnn_seq_backward32(gy, U.t().contiguous(), hs, DG, kind)
+            gh = DG[:, 0] @ U  # dh0 (one product per sequence)
+        else:
+            Ut = NO.transpose_bf16(U)
+            NO.rnn_seq_backward(gy, Ut, hs, DG, kind)
+            gh = NO.gemm(DG[:, 0], Ut)
+        self._grad_hidden_state = [gh]
+        _acc_h2g_grad(h2h, DG.reshape(B * Tn, H), _hprev_rows(h0, out), U)
+        _fire_grad_ready([h2h])
+        self._rec = None
+        return DG
+
+    def _lstmp_backward(self, gradOutput):
+        from ...ops import native_ops as NO
+        _, h0, c0, out, acts, tcs, cs, peep = self._rec
+        cell: LSTMPeephole = self.topology
+        Ug = [l.cw("weight") for l in cell.h2g]
+        B, Tn, H = out.shape
+        gy = gradOutput.to(out.dtype)
+        if not gy.is_contiguous():
+            gy = gy.contiguous()
+        dev = out.device
+        DG = torch.empty(B, Tn, 4 * H, device=dev, dtype=out.dtype)  # (da_i, da_f, da_g, da_o) per step
+        gc = torch.empty(B, H, device=dev, dtype=torch.float32)
+        Ucat = torch.cat(Ug, 0)  # (4H, H): packed once per backward call, as the LSTM path transposes once
+        if out.dtype == torch.float32:
+            NO.lstmp_seq_backward32(gy, Ucat.t().contiguous(), peep, acts, tcs, cs, c0, DG, gc)
+            gh = DG[:, 0] @ Ucat
+        else:
+            Ut = NO.transpose_bf16(Ucat)  # (H, 4H)
+            NO.lstmp_seq_backward(gy, Ut, peep, acts, tcs, cs, c0, DG, gc)
+            gh = NO.gemm(DG[:, 0], Ut)
+        self._grad_hidden_state = [gh, gc]
+        hprev = _hprev_rows(h0, out)
+        for k, (l, U) in enumerate(zip(cell.h2g, Ug)):
+            _acc_h2g_grad(l, DG[:, :, k * H:(k + 1) * H].reshape(B * Tn, H), hprev, U)
+        gps = [m.gradWeight.reshape(H) for m in cell.peep]
+        if any(m.scale_w != 0 for m in cell.peep):
+            if len({m.scale_w for m in cell.peep}) == 1:
+                NO.peephole_grad(DG, cs, c0, *gps, scale=cell.peep[0].scale_w)
+            else:  # per-module scales: one pass into zeroed rows, scaled on the way in
+                tmp = torch.zeros(3, H, device=dev, dtype=torch.float32)
+                NO.peephole_grad(DG, cs, c0, tmp[0], tmp[1], tmp[2])
+                for m, gp, t in zip(cell.peep, gps, tmp):
+                    gp.add_(t, alpha=m.scale_w)
+            for m in cell.peep:
+                if m.wRegularizer is not None and m.scale_w != 0:
+                    m.wRegularizer.accRegularization(m.weight, m.gradWeight, m.scale_w)
+        _fire_grad_ready(cell.h2g + cell.peep)
         self._rec = None
         return DG
 

@@ -18,6 +18,11 @@
 //   3 GRU forward 2  (G=1)  A = rh,       U_h [H][H]:   n = tanh(x_h + rh U_hᵀ), h' = (1−z)n + z h
 //   4 GRU backward 1 (G=1)  A = da_rz_{t+1}, U_rzᵀ [H][2H]: dh' = gy + carry + da_rz U_rz → da_z, da_n
 //   5 GRU backward 2 (G=1)  A = da_n_t,   U_hᵀ [H][H]:  drh = da_n U_h → da_r, carry += drh∘r
+//   6 RNN forward    (G=1)  A = h_{t-1},  U [H][H]:     h = act(x + b_h + h Uᵀ) (+ fp32 save of h)
+//   7 RNN backward   (G=1)  A = da_{t+1}, Uᵀ [H][H]:    da = (gy + da_{t+1} U)·act′(fp32 save)
+//   8 peephole forward  (G=4)  A = h_{t-1}, four blocks U_i, U_f, U_g, U_o [H][H] (RnnStep::ug, read in
+//                              place): DL/nn/LSTMPeephole.scala, gates (i, f, g, o), p_i∘c₋₁, p_f∘c₋₁, p_o∘c
+//   9 peephole backward (G=1)  A = dg_{t+1} [M][4H], Uᵀ [H][4H]: dh = gy + dg_{t+1} U → dg_t, dc_{t-1}
 #include "common.h"
 
 typedef short v8s __attribute__((ext_vector_type(8)));
@@ -61,6 +66,11 @@ struct RnnStep {
   // hprev, h_out, gy, dg, rh) holds fp32 instead, and the products run as bf16x3 on the matrix
   // cores (hi·hi + lo·hi + hi·lo, hi = rne(v), lo = rne(v − hi)) — fp32-accurate recurrent GEMMs
   int f32;
+  // cells 6-9 (RnnCell, LSTMPeephole)
+  const float* bh;       // cell 6: hidden bias row [Hs] (null = none)
+  const float* peep;     // cells 8, 9: peephole weights [3][Hs] (p_i, p_f, p_o)
+  int actk;              // cells 6, 7: 0 Tanh, 1 ReLU, 2 Sigmoid
+  const bf16_t* ug[4];   // cell 8: the four gate blocks U_i, U_f, U_g, U_o, each [Hs][K] (separate parameters)
 };
 
 __device__ __forceinline__ float sgm(float x) { return 1.f / (1.f + __expf(-x)); }
@@ -104,6 +114,18 @@ template <> struct NPre<2> { static constexpr int v = 3; };  // x_r, x_z, h_prev
 template <> struct NPre<3> { static constexpr int v = 3; };  // x_h, h_prev, z
 template <> struct NPre<4> { static constexpr int v = 5; };  // gy, carry, z, n, h_prev
 template <> struct NPre<5> { static constexpr int v = 3; };  // carry, r, h_prev
+template <> struct NPre<6> { static constexpr int v = 2; };  // x, b_h
+template <> struct NPre<7> { static constexpr int v = 2; };  // gy, fp32 h
+template <> struct NPre<8> { static constexpr int v = 8; };  // xg i,f,g,o, c_prev, p_i, p_f, p_o
+template <> struct NPre<9> { static constexpr int v = 11; }; // gy, act i,f,g,o, tanh(c), c_prev, dc_next, p_i, p_f, p_o
+
+// RnnCell activation (RnnStep::actk) and its derivative from the fp32 activation value
+__device__ __forceinline__ float rnn_act(int k, float a) {
+  return k == 0 ? tanhf(a) : (k == 1 ? fmaxf(a, 0.f) : sgm(a));
+}
+__device__ __forceinline__ float rnn_dact(int k, float h) {
+  return k == 0 ? 1.f - h * h : (k == 1 ? (h > 0.f ? 1.f : 0.f) : h * (1.f - h));
+}
 
 // The epilogue's operands are fetched by wave 0 BEFORE the reduction loop so their memory latency
 // overlaps the MFMA chain instead of following it (the step kernels are latency-bound).
@@ -138,10 +160,32 @@ __device__ __forceinline__ void pre_load(const RnnStep& p, int m, int j, float (
     ldf4(p.s1 + mh, v[2]);
     ldf4(p.s2 + mh, v[3]);
     ld4(p.hprev, F32, (long long)m * p.ldhp + j, v[4]);
-  } else {
+  } else if constexpr (CELL == 5) {
     ldf4(p.s0 + mh, v[0]);
     ldf4(p.s1 + mh, v[1]);
     ld4(p.hprev, F32, (long long)m * p.ldhp + j, v[2]);
+  } else if constexpr (CELL == 6) {
+    ld4(p.xg, p.x_f32, (long long)m * p.ldx + j, v[0]);
+    ldf4(p.bh ? p.bh + j : nullptr, v[1]);
+  } else if constexpr (CELL == 7) {
+    ld4(p.gy, F32, (long long)m * p.ldgy + j, v[0]);
+    ldf4(p.s0 + mh, v[1]);
+  } else if constexpr (CELL == 8) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) ld4(p.xg, p.x_f32, (long long)m * p.ldx + g * H + j, v[g]);
+    ldf4(p.c_prev ? p.c_prev + mh : nullptr, v[4]);
+#pragma unroll
+    for (int g = 0; g < 3; ++g) ldf4(p.peep + g * H + j, v[5 + g]);
+  } else {
+    ld4(p.gy, F32, (long long)m * p.ldgy + j, v[0]);
+    const float* a = p.act + (long long)m * 4 * H + j;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) ldf4(a + g * H, v[1 + g]);
+    ldf4(p.tc + mh, v[5]);
+    ldf4(p.c_prev ? p.c_prev + mh : nullptr, v[6]);
+    ldf4(p.gc_next ? p.gc_next + mh : nullptr, v[7]);
+#pragma unroll
+    for (int g = 0; g < 3; ++g) ldf4(p.peep + g * H + j, v[8 + g]);
   }
 }
 
@@ -225,7 +269,7 @@ __device__ __forceinline__ void epilogue(const RnnStep& p, int m, int j, const f
     st4<F32>(p.dg, o + H, daz);
     st4<F32>(p.dg, o + 2 * H, dan);
     stf4(p.s0 + mh, nc);
-  } else {
+  } else if constexpr (CELL == 5) {
     float dar[4], carry[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -235,6 +279,59 @@ __device__ __forceinline__ void epilogue(const RnnStep& p, int m, int j, const f
     }
     st4<F32>(p.dg, (long long)m * p.lddg + j, dar);
     stf4(p.s0 + mh, carry);
+  } else if constexpr (CELL == 6) {
+    float h[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = rnn_act(p.actk, v[0][e] + v[1][e] + acc[0][e]);
+    st4<F32>(p.h_out, (long long)m * p.ldho + j, h);
+    if (p.s0) stf4(p.s0 + mh, h);  // the derivative's source: h before the bf16 rounding
+  } else if constexpr (CELL == 7) {
+    float da[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) da[e] = (v[0][e] + acc[0][e]) * rnn_dact(p.actk, v[1][e]);
+    st4<F32>(p.dg, (long long)m * p.lddg + j, da);
+  } else if constexpr (CELL == 8) {
+    float gi[4], gf[4], gg[4], go[4], h[4], c[4], tcv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float cp = v[4][e];
+      gi[e] = sgm(v[0][e] + acc[0][e] + v[5][e] * cp);
+      gf[e] = sgm(v[1][e] + acc[1][e] + v[6][e] * cp);
+      gg[e] = tanhf(v[2][e] + acc[2][e]);
+      c[e] = gf[e] * cp + gi[e] * gg[e];
+      go[e] = sgm(v[3][e] + acc[3][e] + v[7][e] * c[e]);
+      tcv[e] = tanhf(c[e]);
+      h[e] = go[e] * tcv[e];
+    }
+    st4<F32>(p.h_out, (long long)m * p.ldho + j, h);
+    if (p.c_out) stf4(p.c_out + mh, c);
+    if (p.act) {
+      float* a = p.act + (long long)m * 4 * H + j;
+      stf4(a, gi);
+      stf4(a + H, gf);
+      stf4(a + 2 * H, gg);
+      stf4(a + 3 * H, go);
+    }
+    if (p.tc) stf4(p.tc + mh, tcv);
+  } else {
+    float di[4], df[4], dgg[4], dout[4], dcp[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float i = v[1][e], f = v[2][e], g = v[3][e], o = v[4][e], tcv = v[5][e];
+      const float d_h = v[0][e] + acc[0][e];
+      dout[e] = d_h * tcv * o * (1.f - o);
+      const float dc = d_h * o * (1.f - tcv * tcv) + v[7][e] + dout[e] * v[10][e];
+      di[e] = dc * g * i * (1.f - i);
+      df[e] = dc * v[6][e] * f * (1.f - f);
+      dgg[e] = dc * i * (1.f - g * g);
+      dcp[e] = dc * f + di[e] * v[8][e] + df[e] * v[9][e];
+    }
+    const long long o = (long long)m * p.lddg + j;
+    st4<F32>(p.dg, o, di);
+    st4<F32>(p.dg, o + H, df);
+    st4<F32>(p.dg, o + 2 * H, dgg);
+    st4<F32>(p.dg, o + 3 * H, dout);
+    stf4(p.dc_prev + mh, dcp);
   }
 }
 
@@ -311,7 +408,11 @@ __device__ __forceinline__ void rnn_step_body(const RnnStep& p) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
           v8s wh, wl;
-          split_x3(wu ? wu + g * gs + kk : nullptr, kin && bu && wu, wh, wl);
+          if constexpr (CELL == 8)  // the gate's own block (no second segment for this cell)
+            split_x3(reinterpret_cast<const float*>(p.ug[g]) + (long long)(bu ? j0 + fr : 0) * p.K + kk, kin && bu, wh,
+                     wl);
+          else
+            split_x3(wu ? wu + g * gs + kk : nullptr, kin && bu && wu, wh, wl);
           acc0[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh0, acc0[g], 0, 0, 0);
           acc1[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh1, acc1[g], 0, 0, 0);
           acc0[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh0, acc0[g], 0, 0, 0);
@@ -365,7 +466,12 @@ __device__ __forceinline__ void rnn_step_body(const RnnStep& p) {
       const long long gs = seg2 ? gstride2 : gstride;
       v8s w[G];
 #pragma unroll
-      for (int g = 0; g < G; ++g) w[g] = (kin && bu) ? *reinterpret_cast<const v8s*>(wu + g * gs + kk) : zero;
+      for (int g = 0; g < G; ++g) {
+        if constexpr (CELL == 8)  // the gate's own block (no second segment for this cell)
+          w[g] = (kin && bu) ? *reinterpret_cast<const v8s*>(p.ug[g] + (long long)(j0 + fr) * p.K + kk) : zero;
+        else
+          w[g] = (kin && bu) ? *reinterpret_cast<const v8s*>(wu + g * gs + kk) : zero;
+      }
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         acc0[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[g], x0, acc0[g], 0, 0, 0);
@@ -401,6 +507,29 @@ __global__ void __launch_bounds__(64 * kStepWaves) k_rnn_step(RnnStep p) {
   rnn_step_body<CELL, G, F32>(p);
 }
 
+// Cells 6-9 (and the peephole-gradient kernels below) are explicit specialisations so that they alone
+// carry a per-kernel code-generation attribute: no packed fp32 (v_pk_*_f32) instruction selection for
+// their scalar epilogue chains.  Cells 0-5 and every other kernel of this file keep the default.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BIGDL_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define BIGDL_NO_PK_F32
+#endif
+#define BIGDL_RNN_CELL_KERNEL(CELL, G, F32)                                                          \
+  template <>                                                                                         \
+  __global__ void __launch_bounds__(64 * kStepWaves) BIGDL_NO_PK_F32 k_rnn_step<CELL, G, F32>(RnnStep p) { \
+    rnn_step_body<CELL, G, F32>(p);                                                                   \
+  }
+BIGDL_RNN_CELL_KERNEL(6, 1, false)
+BIGDL_RNN_CELL_KERNEL(6, 1, true)
+BIGDL_RNN_CELL_KERNEL(7, 1, false)
+BIGDL_RNN_CELL_KERNEL(7, 1, true)
+BIGDL_RNN_CELL_KERNEL(8, 4, false)
+BIGDL_RNN_CELL_KERNEL(8, 4, true)
+BIGDL_RNN_CELL_KERNEL(9, 1, false)
+BIGDL_RNN_CELL_KERNEL(9, 1, true)
+#undef BIGDL_RNN_CELL_KERNEL
+
 // Two stacked layers in ONE launch (blockIdx.z = layer; bit z of `live` = that layer has a step in
 // this wave): the layer wavefront — layer 1 runs step t−1 while layer 0 runs step t (forward), layer 0
 // runs step t+1 while layer 1 runs step t (backward, reversed), so a 2-layer sequence takes T + 1
@@ -421,14 +550,14 @@ static bool a8(const void* q) { return ((uintptr_t)q & 7) == 0; }
 // operand rows, 8-B aligned bf16 / 16-B aligned fp32 quads), before any launch.
 static int rnn_step_check(int cell, const RnnStep& p) {
   const int M = p.M, K = p.K, Hs = p.Hs;
-  if (M <= 0 || K <= 0 || Hs <= 0 || Hs % 8 || K % 8 || cell < 0 || cell > 5) return (int)hipErrorInvalidValue;
+  if (M <= 0 || K <= 0 || Hs <= 0 || Hs % 8 || K % 8 || cell < 0 || cell > 9) return (int)hipErrorInvalidValue;
   if (p.a && (p.lda < K || p.lda % 8 || !a16(p.a))) return (int)hipErrorInvalidValue;
   if (!p.u || !a16(p.u)) return (int)hipErrorInvalidValue;
-  static const int KWANT[6] = {1, 4, 1, 1, 2, 1};  // K in units of Hs
+  static const int KWANT[10] = {1, 4, 1, 1, 2, 1, 1, 1, 1, 4};  // K in units of Hs
   if (K != KWANT[cell] * Hs) return (int)hipErrorInvalidValue;
   if (p.K2 < 0 || p.K2 % 8 || (p.K2 && (!p.u2 || !a16(p.u2))) || (!p.K2 && p.a2)) return (int)hipErrorInvalidValue;
   if (p.a2 && (p.lda2 < p.K2 || p.lda2 % 8 || !a16(p.a2))) return (int)hipErrorInvalidValue;
-  const void* f32s[] = {p.c_prev, p.c_out, p.act, p.tc, p.gc_next, p.dc_prev, p.s0, p.s1, p.s2};
+  const void* f32s[] = {p.c_prev, p.c_out, p.act, p.tc, p.gc_next, p.dc_prev, p.s0, p.s1, p.s2, p.bh, p.peep};
   for (const void* q : f32s)
     if (q && !a16(q)) return (int)hipErrorInvalidValue;
   if (p.xg && (p.ldx % 4 || (p.x_f32 ? !a16(p.xg) : !a8(p.xg)))) return (int)hipErrorInvalidValue;
@@ -445,6 +574,15 @@ static int rnn_step_check(int cell, const RnnStep& p) {
     case 3: ok = p.xg && p.hprev && p.s1 && p.h_out; break;
     case 4: ok = p.gy && p.s0 && p.s1 && p.s2 && p.hprev && p.dg; break;
     case 5: ok = p.a && p.s0 && p.s1 && p.hprev && p.dg; break;
+    case 6: ok = p.xg && p.h_out; break;
+    case 7: ok = p.gy && p.s0 && p.dg; break;
+    case 8: ok = p.xg && p.h_out && p.peep; break;
+    case 9: ok = p.gy && p.act && p.tc && p.dg && p.dc_prev && p.peep; break;
+  }
+  if (cell >= 6) {  // the new cells: one reduction segment, a known activation, cell 8's four gate blocks
+    ok = ok && !p.K2 && !p.a2 && p.actk >= 0 && p.actk <= 2;
+    if (cell == 8)
+      for (const bf16_t* q : p.ug) ok = ok && q && a16(q);
   }
   return ok ? 0 : (int)hipErrorInvalidValue;
 }
@@ -453,13 +591,25 @@ static dim3 rnn_step_grid(int Hs, int M, int z = 1) {
   return dim3((unsigned)((Hs + 15) / 16), (unsigned)((M + 31) / 32), (unsigned)z);
 }
 
+// the operands only cells 6-9 take (RnnStep::bh, peep, actk, ug)
+struct RnnCellX {
+  const float* bh;
+  const float* peep;
+  int actk;
+  const void* ug[4];
+};
+
 static int rnn_step_run(int cell, const void* a, long long lda, const void* u, int M, int K, int Hs, const void* xg,
                         long long ldx, int x_f32, const void* hprev, long long ldhp, const float* c_prev, void* h_out,
                         long long ldho, float* c_out, float* act, float* tc, const void* gy, long long ldgy,
                         const float* gc_next, void* dg, long long lddg, float* dc_prev, float* s0, float* s1, float* s2,
-                        void* rh, long long ldrh, int f32, hipStream_t s) {
+                        void* rh, long long ldrh, int f32, hipStream_t s, const RnnCellX* x = nullptr) {
   RnnStep p{};  // value-initialised: the second segment stays off
   p.f32 = f32;
+  if (x) {
+    p.bh = x->bh; p.peep = x->peep; p.actk = x->actk;
+    for (int g = 0; g < 4; ++g) p.ug[g] = (const bf16_t*)x->ug[g];
+  }
   p.a = (const bf16_t*)a; p.lda = lda; p.u = (const bf16_t*)u; p.M = M; p.K = K; p.Hs = Hs;
   p.xg = xg; p.ldx = ldx; p.x_f32 = x_f32; p.hprev = (const bf16_t*)hprev; p.ldhp = ldhp; p.c_prev = c_prev;
   p.h_out = (bf16_t*)h_out; p.ldho = ldho; p.c_out = c_out; p.act = act; p.tc = tc; p.gy = (const bf16_t*)gy;
@@ -475,7 +625,11 @@ static int rnn_step_run(int cell, const void* a, long long lda, const void* u, i
       case 2: hipLaunchKernelGGL((k_rnn_step<2, 2, true>), grid, block, 0, s, p); break;
       case 3: hipLaunchKernelGGL((k_rnn_step<3, 1, true>), grid, block, 0, s, p); break;
       case 4: hipLaunchKernelGGL((k_rnn_step<4, 1, true>), grid, block, 0, s, p); break;
-      default: hipLaunchKernelGGL((k_rnn_step<5, 1, true>), grid, block, 0, s, p); break;
+      case 5: hipLaunchKernelGGL((k_rnn_step<5, 1, true>), grid, block, 0, s, p); break;
+      case 6: hipLaunchKernelGGL((k_rnn_step<6, 1, true>), grid, block, 0, s, p); break;
+      case 7: hipLaunchKernelGGL((k_rnn_step<7, 1, true>), grid, block, 0, s, p); break;
+      case 8: hipLaunchKernelGGL((k_rnn_step<8, 4, true>), grid, block, 0, s, p); break;
+      default: hipLaunchKernelGGL((k_rnn_step<9, 1, true>), grid, block, 0, s, p); break;
     }
   } else {
     switch (cell) {
@@ -484,7 +638,11 @@ static int rnn_step_run(int cell, const void* a, long long lda, const void* u, i
       case 2: hipLaunchKernelGGL((k_rnn_step<2, 2>), grid, block, 0, s, p); break;
       case 3: hipLaunchKernelGGL((k_rnn_step<3, 1>), grid, block, 0, s, p); break;
       case 4: hipLaunchKernelGGL((k_rnn_step<4, 1>), grid, block, 0, s, p); break;
-      default: hipLaunchKernelGGL((k_rnn_step<5, 1>), grid, block, 0, s, p); break;
+      case 5: hipLaunchKernelGGL((k_rnn_step<5, 1>), grid, block, 0, s, p); break;
+      case 6: hipLaunchKernelGGL((k_rnn_step<6, 1>), grid, block, 0, s, p); break;
+      case 7: hipLaunchKernelGGL((k_rnn_step<7, 1>), grid, block, 0, s, p); break;
+      case 8: hipLaunchKernelGGL((k_rnn_step<8, 4>), grid, block, 0, s, p); break;
+      default: hipLaunchKernelGGL((k_rnn_step<9, 1>), grid, block, 0, s, p); break;
     }
   }
   BIGDL_CHECK_LAUNCH();
@@ -498,6 +656,20 @@ BIGDL_EXPORT int bigdl_rnn_step(int cell, const void* a, long long lda, const vo
                                 hipStream_t s) {
   return rnn_step_run(cell, a, lda, u, M, K, Hs, xg, ldx, x_f32, hprev, ldhp, c_prev, h_out, ldho, c_out, act, tc, gy,
                       ldgy, gc_next, dg, lddg, dc_prev, s0, s1, s2, rh, ldrh, 0, s);
+}
+
+// One step of cells 6-9 (RnnCell, LSTMPeephole), bf16 (f32 = 0) or fp32 / bf16x3 (f32 = 1) operands.
+// Cell 8 reads its gate blocks through u_i, u_f, u_g, u_o; the other cells take their weight in u_i.
+BIGDL_EXPORT int bigdl_rnn_cell_step(int cell, int f32, int actk, const void* a, long long lda, const void* u_i,
+                                     const void* u_f, const void* u_g, const void* u_o, int M, int K, int Hs,
+                                     const void* xg, long long ldx, int x_f32, const float* bh, const float* peep,
+                                     const float* c_prev, void* h_out, long long ldho, float* c_out, float* act,
+                                     float* tc, const void* gy, long long ldgy, const float* gc_next, void* dg,
+                                     long long lddg, float* dc_prev, float* s0, hipStream_t s) {
+  if (cell < 6 || cell > 9) return (int)hipErrorInvalidValue;
+  const RnnCellX x{bh, peep, actk, {u_i, u_f, u_g, u_o}};
+  return rnn_step_run(cell, a, lda, u_i, M, K, Hs, xg, ldx, x_f32, nullptr, 0, c_prev, h_out, ldho, c_out, act, tc, gy,
+                      ldgy, gc_next, dg, lddg, dc_prev, s0, nullptr, nullptr, nullptr, 0, f32, s, &x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1825,4 +1997,241 @@ BIGDL_EXPORT int bigdl_gru_seq_bwd32(const float* gy, const float* Urz_t, const 
   if (B <= 0 || T <= 0 || H <= 0 || !gy || !Urz_t || !Uh_t || !R || !Z || !Nn || !out || !h0 || !DG || !carry)
     return (int)hipErrorInvalidValue;
   return gru_bwd_steps(gy, Urz_t, Uh_t, R, Z, Nn, out, h0, DG, carry, B, T, H, 1, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// RnnCell (DL/nn/RNN.scala) and LSTMPeephole (DL/nn/LSTMPeephole.scala) whole sequences: one cell
+// 6 / 7 / 8 / 9 launch per step.  Layouts as the LSTM launchers; x2 [B][T][H] (RNN) / [B][T][4H] in
+// block order (i, f, g, o) (peephole); the RNN's fp32 save hs [T][B][H] (null = inference); the
+// peephole saves cs / acts / tcs as the LSTM's (inference: cbuf ping-pong); null c0 = zero.
+// ------------------------------------------------------------------------------------------------
+static int rnn_fwd_steps(const void* x2, int x_f32, const void* h0, const float* bh, const void* U, void* out,
+                         float* hs, int actk, int B, int T, int H, int f32, hipStream_t s) {
+  if (B <= 0 || T <= 0 || H <= 0 || !x2 || !h0 || !U || !out) return (int)hipErrorInvalidValue;
+  const RnnCellX x{bh, nullptr, actk, {}};
+  const long long BH = (long long)B * H;
+  const int esz = x_f32 ? 4 : 2;
+  for (int t = 0; t < T; ++t) {
+    const void* a = t == 0 ? h0 : eo((const void*)out, (long long)(t - 1) * H, f32);
+    int rc = rnn_step_run(6, a, t == 0 ? H : (long long)T * H, U, B, H, H, (const char*)x2 + (long long)t * H * esz,
+                          (long long)T * H, x_f32, nullptr, 0, nullptr, eo(out, (long long)t * H, f32), (long long)T * H,
+                          nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, hs ? hs + t * BH : nullptr,
+                          nullptr, nullptr, nullptr, 0, f32, s, &x);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+static int rnn_bwd_steps(const void* gy, const void* Ut, const float* hs, void* DG, int actk, int B, int T, int H,
+                         int f32, hipStream_t s) {
+  if (B <= 0 || T <= 0 || H <= 0 || !gy || !Ut || !hs || !DG) return (int)hipErrorInvalidValue;
+  const RnnCellX x{nullptr, nullptr, actk, {}};
+  const long long BH = (long long)B * H;
+  for (int t = T - 1; t >= 0; --t) {
+    const bool last = t + 1 == T;
+    int rc = rnn_step_run(7, last ? nullptr : eo((const void*)DG, (long long)(t + 1) * H, f32), (long long)T * H, Ut, B,
+                          H, H, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                          eo(gy, (long long)t * H, f32), (long long)T * H, nullptr, eo(DG, (long long)t * H, f32),
+                          (long long)T * H, nullptr, (float*)hs + t * BH, nullptr, nullptr, nullptr, 0, f32, s, &x);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+BIGDL_EXPORT int bigdl_rnn_seq_fwd(const void* x2, int x_f32, const void* h0, const float* bh, const void* U, void* out,
+                                   float* hs, int actk, int B, int T, int H, hipStream_t s) {
+  return rnn_fwd_steps(x2, x_f32, h0, bh, U, out, hs, actk, B, T, H, 0, s);
+}
+BIGDL_EXPORT int bigdl_rnn_seq_fwd32(const float* x2, const float* h0, const float* bh, const float* U, float* out,
+                                     float* hs, int actk, int B, int T, int H, hipStream_t s) {
+  return rnn_fwd_steps(x2, 1, h0, bh, U, out, hs, actk, B, T, H, 1, s);
+}
+BIGDL_EXPORT int bigdl_rnn_seq_bwd(const void* gy, const void* Ut, const float* hs, void* DG, int actk, int B, int T,
+                                   int H, hipStream_t s) {
+  return rnn_bwd_steps(gy, Ut, hs, DG, actk, B, T, H, 0, s);
+}
+BIGDL_EXPORT int bigdl_rnn_seq_bwd32(const float* gy, const float* Ut, const float* hs, float* DG, int actk, int B,
+                                     int T, int H, hipStream_t s) {
+  return rnn_bwd_steps(gy, Ut, hs, DG, actk, B, T, H, 1, s);
+}
+
+static int lstmp_fwd_steps(const void* x2, int x_f32, const void* h0, const float* c0, const void* const* Ug,
+                           const float* peep, void* out, float* cs, float* acts, float* tcs, float* cbuf, int B, int T,
+                           int H, int f32, hipStream_t s) {
+  if (B <= 0 || T <= 0 || H <= 0 || !x2 || !h0 || !peep || !out) return (int)hipErrorInvalidValue;
+  const bool train = cs && acts && tcs;
+  if (!train && !cbuf) return (int)hipErrorInvalidValue;
+  const RnnCellX x{nullptr, peep, 0, {Ug[0], Ug[1], Ug[2], Ug[3]}};
+  const long long G = 4LL * H, BH = (long long)B * H;
+  const int esz = x_f32 ? 4 : 2;
+  for (int t = 0; t < T; ++t) {
+    const void* a = t == 0 ? h0 : eo((const void*)out, (long long)(t - 1) * H, f32);
+    const float* cp = t == 0 ? c0 : (train ? cs + (t - 1) * BH : cbuf + ((t - 1) & 1) * BH);
+    int rc = rnn_step_run(8, a, t == 0 ? H : (long long)T * H, Ug[0], B, H, H, (const char*)x2 + (long long)t * G * esz,
+                          (long long)T * G, x_f32, nullptr, 0, cp, eo(out, (long long)t * H, f32), (long long)T * H,
+                          train ? cs + t * BH : cbuf + (t & 1) * BH, train ? acts + t * B * G : nullptr,
+                          train ? tcs + t * BH : nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, 0, f32, s, &x);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+static int lstmp_bwd_steps(const void* gy, const void* Ut, const float* peep, const float* acts, const float* tcs,
+                           const float* cs, const float* c0, void* DG, float* gc, int B, int T, int H, int f32,
+                           hipStream_t s) {
+  if (B <= 0 || T <= 0 || H <= 0 || !gy || !Ut || !peep || !acts || !tcs || !cs || !DG || !gc)
+    return (int)hipErrorInvalidValue;
+  const RnnCellX x{nullptr, peep, 0, {}};
+  const long long G = 4LL * H, BH = (long long)B * H;
+  for (int t = T - 1; t >= 0; --t) {
+    const bool last = t + 1 == T;
+    int rc = rnn_step_run(9, last ? nullptr : eo((const void*)DG, (t + 1) * G, f32), (long long)T * G, Ut, B, (int)G, H,
+                          nullptr, 0, 0, nullptr, 0, t > 0 ? cs + (t - 1) * BH : c0, nullptr, 0, nullptr,
+                          (float*)acts + t * B * G, (float*)tcs + t * BH, eo(gy, (long long)t * H, f32), (long long)T * H,
+                          last ? nullptr : gc, eo(DG, t * G, f32), (long long)T * G, gc, nullptr, nullptr, nullptr,
+                          nullptr, 0, f32, s, &x);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+BIGDL_EXPORT int bigdl_lstmp_seq_fwd(const void* x2, int x_f32, const void* h0, const float* c0, const void* u_i,
+                                     const void* u_f, const void* u_g, const void* u_o, const float* peep, void* out,
+                                     float* cs, float* acts, float* tcs, float* cbuf, int B, int T, int H,
+                                     hipStream_t s) {
+  const void* Ug[4] = {u_i, u_f, u_g, u_o};
+  return lstmp_fwd_steps(x2, x_f32, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf, B, T, H, 0, s);
+}
+BIGDL_EXPORT int bigdl_lstmp_seq_fwd32(const float* x2, const float* h0, const float* c0, const float* u_i,
+                                       const float* u_f, const float* u_g, const float* u_o, const float* peep,
+                                       float* out, float* cs, float* acts, float* tcs, float* cbuf, int B, int T, int H,
+                                       hipStream_t s) {
+  const void* Ug[4] = {u_i, u_f, u_g, u_o};
+  return lstmp_fwd_steps(x2, 1, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf, B, T, H, 1, s);
+}
+BIGDL_EXPORT int bigdl_lstmp_seq_bwd(const void* gy, const void* Ut, const float* peep, const float* acts,
+                                     const float* tcs, const float* cs, const float* c0, void* DG, float* gc, int B,
+                                     int T, int H, hipStream_t s) {
+  return lstmp_bwd_steps(gy, Ut, peep, acts, tcs, cs, c0, DG, gc, B, T, H, 0, s);
+}
+BIGDL_EXPORT int bigdl_lstmp_seq_bwd32(const float* gy, const float* Ut, const float* peep, const float* acts,
+                                       const float* tcs, const float* cs, const float* c0, float* DG, float* gc, int B,
+                                       int T, int H, hipStream_t s) {
+  return lstmp_bwd_steps(gy, Ut, peep, acts, tcs, cs, c0, DG, gc, B, T, H, 1, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Peephole-weight gradient (the three CMul(H) of LSTMPeephole): per hidden unit j
+//   gp_i[j] += s·Σ_{b,t} DG_i[b,t,j]·c_{t-1}[b,j]   gp_f[j] += s·Σ DG_f·c_{t-1}   gp_o[j] += s·Σ DG_o·c_t
+// over DG [B][T][4H] (bf16 or fp32, block order i, f, g, o) and the fp32 cs [T][B][H] / c0 (null = 0).
+// A column reduction over the B·T rows.  A workgroup is 32 column lanes × 8 row lanes: a column lane
+// owns 8 consecutive units (one 16-byte read per gate of a bf16 row, two of an fp32 row, and two
+// 16-byte reads each of c_{t-1} and c_t), so a wave's rows are read as contiguous 16-byte pieces; a
+// row lane walks every 8th row of the workgroup's kPgRows-row chunk.  The 8 row lanes fold through LDS
+// in lane order into one partial row per chunk, and k_peephole_fold adds the chunks in index order:
+// fp32 accumulation, no atomics, the same bits on every run.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPgRows = 32;   // rows of (b, t) per workgroup
+constexpr int kPgCols = 256;  // units per workgroup (32 column lanes × 8)
+
+__device__ __forceinline__ void ld8(const void* base, int f32, long long off, float* o) {
+  if (f32) {
+    ld4(base, 1, off, o);
+    ld4(base, 1, off + 4, o + 4);
+  } else {
+    const uint4 v = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + off);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      o[2 * q] = __uint_as_float(w[q] << 16);
+      o[2 * q + 1] = __uint_as_float(w[q] & 0xFFFF0000u);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) BIGDL_NO_PK_F32 k_peephole_partial(const void* __restrict__ DG, int dg_f32,
+                                                          const float* __restrict__ cs, const float* __restrict__ c0,
+                                                          float* __restrict__ part, int B, int T, int H) {
+  __shared__ float red[7][3][kPgCols];
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+  const int j = blockIdx.y * kPgCols + cl * 8;  // row chunks on grid.x (no 65535 limit), unit tiles on grid.y
+  const long long n = (long long)B * T;
+  const long long r0 = (long long)blockIdx.x * kPgRows;
+  float acc[3][8];
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
+  if (j < H) {  // H % 8 == 0: a lane's 8 units are all in or all out
+    for (int k = rl; k < kPgRows; k += 8) {
+      const long long r = r0 + k;
+      if (r >= n) break;
+      const long long b = r / T, t = r % T;
+      float di[8], df[8], dout[8], cp[8], cc[8];
+      const long long o = r * 4 * H + j;
+      ld8(DG, dg_f32, o, di);
+      ld8(DG, dg_f32, o + H, df);
+      ld8(DG, dg_f32, o + 3LL * H, dout);
+      const float* pc = t > 0 ? cs + ((t - 1) * B + b) * H + j : (c0 ? c0 + b * H + j : nullptr);
+      ldf4(pc, cp);
+      ldf4(pc ? pc + 4 : nullptr, cp + 4);
+      const float* pn = cs + (t * B + b) * H + j;
+      ldf4(pn, cc);
+      ldf4(pn + 4, cc + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        acc[0][e] += di[e] * cp[e];
+        acc[1][e] += df[e] * cp[e];
+        acc[2][e] += dout[e] * cc[e];
+      }
+    }
+  }
+  if (rl > 0) {
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[rl - 1][g][cl * 8 + e] = acc[g][e];
+  }
+  __syncthreads();
+  if (rl > 0 || j >= H) return;
+#pragma unroll
+  for (int w = 0; w < 7; ++w)
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[g][e] += red[w][g][cl * 8 + e];
+  float* o = part + (long long)blockIdx.x * 3 * H + j;  // part [chunks][3][H]
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    stf4(o + (long long)g * H, acc[g]);
+    stf4(o + (long long)g * H + 4, acc[g] + 4);
+  }
+}
+
+__global__ void __launch_bounds__(256) BIGDL_NO_PK_F32 k_peephole_fold(const float* __restrict__ part, int chunks, float* gp_i,
+                                                       float* gp_f, float* gp_o, float scale, int H) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 3 * H) return;
+  float a = 0.f;
+  for (int c = 0; c < chunks; ++c) a += part[(long long)c * 3 * H + i];
+  const int g = i / H, j = i - g * H;
+  float* gp = g == 0 ? gp_i : (g == 1 ? gp_f : gp_o);
+  gp[j] += scale * a;
+}
+
+// part: at least ⌈B·T / 32⌉·3·H floats of workspace (fully written before it is read)
+BIGDL_EXPORT int bigdl_peephole_grad(const void* DG, int dg_f32, const float* cs, const float* c0, float* gp_i,
+                                     float* gp_f, float* gp_o, float scale, float* part, long long npart, int B, int T,
+                                     int H, hipStream_t s) {
+  if (B <= 0 || T <= 0 || H <= 0 || H % 8 || !DG || !cs || !gp_i || !gp_f || !gp_o || !part)
+    return (int)hipErrorInvalidValue;
+  if (!a16(DG) || !a16(cs) || (c0 && !a16(c0)) || !a16(part)) return (int)hipErrorInvalidValue;
+  const long long n = (long long)B * T, chunks = (n + kPgRows - 1) / kPgRows;
+  if (chunks > 0x7fffffff || npart < chunks * 3 * H) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_peephole_partial, dim3((unsigned)chunks, (unsigned)((H + kPgCols - 1) / kPgCols)), dim3(256), 0,
+                     s, DG, dg_f32, cs, c0, part, B, T, H);
+  hipLaunchKernelGGL(k_peephole_fold, dim3((unsigned)((3 * H + 255) / 256)), dim3(256), 0, s, (const float*)part,
+                     (int)chunks, gp_i, gp_f, gp_o, scale, H);
+  BIGDL_CHECK_LAUNCH();
 }

@@ -3138,7 +3138,10 @@ def embedding_backward(grad_weight, idx_1b, gy, scale=1.0, padding_value=0):
 
 
 # ---------------------------------------------------------------------------------- K14/K15 fused recurrent step
-_RNN_CELLS = {"lstm_fwd": 0, "lstm_bwd": 1, "gru_fwd1": 2, "gru_fwd2": 3, "gru_bwd1": 4, "gru_bwd2": 5}
+_RNN_CELLS = {"lstm_fwd": 0, "lstm_bwd": 1, "gru_fwd1": 2, "gru_fwd2": 3, "gru_bwd1": 4, "gru_bwd2": 5,
+              "rnn_fwd": 6, "rnn_bwd": 7, "lstmp_fwd": 8, "lstmp_bwd": 9}
+#: RnnCell activations the step kernels evaluate (RnnStep::actk)
+RNN_ACTS = {"Tanh": 0, "ReLU": 1, "Sigmoid": 2}
 
 
 def _ld(t):
@@ -3146,11 +3149,27 @@ def _ld(t):
 
 
 def rnn_step(cell, a, u, M, K, Hs, xg=None, hprev=None, c_prev=None, h_out=None, c_out=None, act=None, tc=None,
-             gy=None, gc_next=None, dg=None, dc_prev=None, s0=None, s1=None, s2=None, rh=None):
+             gy=None, gc_next=None, dg=None, dc_prev=None, s0=None, s1=None, s2=None, rh=None, bh=None, peep=None,
+             act_kind="Tanh"):
     """One fused recurrent step (rnn_step.hip).  Row operands are 2-D views (unit column stride);
     fp32 state tensors are contiguous [M][Hs] (act [M][4Hs]).  The launcher re-validates every
-    alignment / stride the kernel assumes and returns an error instead of launching."""
+    alignment / stride the kernel assumes and returns an error instead of launching.
+
+    Cells ``rnn_*`` / ``lstmp_*`` (RnnCell, LSTMPeephole) also take the fp32 hidden bias row ``bh``
+    [Hs], the peephole table ``peep`` [3][Hs] (i, f, o) and ``act_kind``; ``lstmp_fwd`` takes ``u`` as
+    the four gate blocks (U_i, U_f, U_g, U_o), each [Hs][K], read in place; fp32 weights select the
+    bf16x3 form."""
     x_f32 = 1 if (xg is not None and xg.dtype == _f32) else 0
+    if _RNN_CELLS[cell] >= 6:
+        ug = list(u) if isinstance(u, (tuple, list)) else [u, None, None, None]
+        check(_lib().bigdl_rnn_cell_step(C.c_int(_RNN_CELLS[cell]), C.c_int(1 if ug[0].dtype == _f32 else 0),
+                                         C.c_int(RNN_ACTS[act_kind]), ptr(a), _ll(_ld(a)), ptr(ug[0]), ptr(ug[1]),
+                                         ptr(ug[2]), ptr(ug[3]), C.c_int(M), C.c_int(K), C.c_int(Hs), ptr(xg),
+                                         _ll(_ld(xg)), C.c_int(x_f32), ptr(bh), ptr(peep), ptr(c_prev), ptr(h_out),
+                                         _ll(_ld(h_out)), ptr(c_out), ptr(act), ptr(tc), ptr(gy), _ll(_ld(gy)),
+                                         ptr(gc_next), ptr(dg), _ll(_ld(dg)), ptr(dc_prev), ptr(s0), _s()),
+              f"rnn_step[{cell}]")
+        return
     check(_lib().bigdl_rnn_step(C.c_int(_RNN_CELLS[cell]), ptr(a), _ll(_ld(a)), ptr(u), C.c_int(M), C.c_int(K),
                                 C.c_int(Hs), ptr(xg), _ll(_ld(xg)), C.c_int(x_f32), ptr(hprev), _ll(_ld(hprev)),
                                 ptr(c_prev), ptr(h_out), _ll(_ld(h_out)), ptr(c_out), ptr(act), ptr(tc), ptr(gy),
@@ -3161,6 +3180,9 @@ def rnn_step(cell, a, u, M, K, Hs, xg=None, hprev=None, c_prev=None, h_out=None,
 def _dense_bf16(*ts):
     return all(t is None or (t.is_cuda and t.is_contiguous() and _al16(t)) for t in ts)
 
+
+#: the density / alignment contract the whole-sequence launchers assert, for eligibility checks
+rnn_dense_ok = _dense_bf16
 
 _RNN_SYNC = {}
 
@@ -3303,6 +3325,111 @@ def rnn_fast_ok(H, *ts):
     if H % 8 or not N.has("lstm_cell_forward"):
         return False
     return all(t is None or (t.is_cuda and t.dtype == _bf16) for t in ts)
+
+
+# RnnCell / LSTMPeephole whole sequences (rnn_step.hip cells 6-9).  One function per direction serves
+# both operand types: the ``32`` names assert fp32 operands (bf16x3 products), the plain ones bf16
+# (x2 may be fp32 either way).
+def _rnn_seq_fwd(f32, x2, h0, bh, U, out, hs, act_kind):
+    B, T, H = x2.shape
+    assert _dense_bf16(x2, h0, bh, U, out, hs) and tuple(out.shape) == (B, T, H) and tuple(U.shape) == (H, H) \
+        and U.dtype == (_f32 if f32 else _bf16) and out.dtype == U.dtype and h0.dtype == U.dtype, "rnn_seq_forward"
+    dims = (C.c_int(RNN_ACTS[act_kind]), C.c_int(B), C.c_int(T), C.c_int(H), _s())
+    if f32:
+        check(_lib().bigdl_rnn_seq_fwd32(ptr(x2), ptr(h0), ptr(bh), ptr(U), ptr(out), ptr(hs), *dims), "rnn_seq_fwd32")
+    else:
+        check(_lib().bigdl_rnn_seq_fwd(ptr(x2), C.c_int(1 if x2.dtype == _f32 else 0), ptr(h0), ptr(bh), ptr(U),
+                                       ptr(out), ptr(hs), *dims), "rnn_seq_fwd")
+
+
+def rnn_seq_forward(x2, h0, bh, U, out, hs, act_kind="Tanh"):
+    """Whole-sequence RnnCell forward (bigdl_rnn_seq_fwd): h_t = act(x2_t + b_h + h_{t-1}·Uᵀ), x2 / out
+    [B][T][H]; ``bh`` fp32 [H] or None; training saves the fp32 h_t in ``hs`` [T][B][H] (None =
+    inference)."""
+    _rnn_seq_fwd(False, x2, h0, bh, U, out, hs, act_kind)
+
+
+def rnn_seq_forward32(x2, h0, bh, U, out, hs, act_kind="Tanh"):
+    _rnn_seq_fwd(True, x2, h0, bh, U, out, hs, act_kind)
+
+
+def _rnn_seq_bwd(f32, gy, Ut, hs, DG, act_kind):
+    B, T, H = gy.shape
+    assert _dense_bf16(gy, Ut, hs, DG) and tuple(DG.shape) == (B, T, H) and tuple(hs.shape) == (T, B, H) \
+        and gy.dtype == (_f32 if f32 else _bf16) and Ut.dtype == gy.dtype and DG.dtype == gy.dtype, "rnn_seq_backward"
+    fn = _lib().bigdl_rnn_seq_bwd32 if f32 else _lib().bigdl_rnn_seq_bwd
+    check(fn(ptr(gy), ptr(Ut), ptr(hs), ptr(DG), C.c_int(RNN_ACTS[act_kind]), C.c_int(B), C.c_int(T), C.c_int(H), _s()),
+          "rnn_seq_bwd")
+
+
+def rnn_seq_backward(gy, Ut, hs, DG, act_kind="Tanh"):
+    """RnnCell BPTT: DG_t = (gy_t + DG_{t+1}·U)·act′(hs_t); ``Ut`` = Uᵀ [H][H]."""
+    _rnn_seq_bwd(False, gy, Ut, hs, DG, act_kind)
+
+
+def rnn_seq_backward32(gy, Ut, hs, DG, act_kind="Tanh"):
+    _rnn_seq_bwd(True, gy, Ut, hs, DG, act_kind)
+
+
+def _lstmp_seq_fwd(f32, x2, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf):
+    B, T, G = x2.shape
+    H = G // 4
+    dt = _f32 if f32 else _bf16
+    assert _dense_bf16(x2, h0, c0, *Ug, peep, out, cs, acts, tcs, cbuf) and tuple(out.shape) == (B, T, H) \
+        and len(Ug) == 4 and all(tuple(u.shape) == (H, H) and u.dtype == dt for u in Ug) and out.dtype == dt \
+        and h0.dtype == dt and tuple(peep.shape) == (3, H) and peep.dtype == _f32, "lstmp_seq_forward"
+    tail = (ptr(peep), ptr(out), ptr(cs), ptr(acts), ptr(tcs), ptr(cbuf), C.c_int(B), C.c_int(T), C.c_int(H), _s())
+    if f32:
+        check(_lib().bigdl_lstmp_seq_fwd32(ptr(x2), ptr(h0), ptr(c0), *[ptr(u) for u in Ug], *tail), "lstmp_seq_fwd32")
+    else:
+        check(_lib().bigdl_lstmp_seq_fwd(ptr(x2), C.c_int(1 if x2.dtype == _f32 else 0), ptr(h0), ptr(c0),
+                                         *[ptr(u) for u in Ug], *tail), "lstmp_seq_fwd")
+
+
+def lstmp_seq_forward(x2, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf):
+    """Whole-sequence LSTMPeephole forward (bigdl_lstmp_seq_fwd): x2 [B][T][4H] in block order
+    (i, f, g, o); ``Ug`` the four recurrent weights (U_i, U_f, U_g, U_o), each [H][H], read in place;
+    ``peep`` fp32 [3][H] (p_i, p_f, p_o); saves / cbuf as :func:`lstm_seq_forward` (acts in i, f, g, o)."""
+    _lstmp_seq_fwd(False, x2, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf)
+
+
+def lstmp_seq_forward32(x2, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf):
+    _lstmp_seq_fwd(True, x2, h0, c0, Ug, peep, out, cs, acts, tcs, cbuf)
+
+
+def _lstmp_seq_bwd(f32, gy, Ut, peep, acts, tcs, cs, c0, DG, gc):
+    B, T, H = gy.shape
+    assert _dense_bf16(gy, Ut, peep, acts, tcs, cs, c0, DG, gc) and tuple(Ut.shape) == (H, 4 * H) \
+        and tuple(DG.shape) == (B, T, 4 * H) and gy.dtype == (_f32 if f32 else _bf16) and Ut.dtype == gy.dtype \
+        and DG.dtype == gy.dtype and tuple(peep.shape) == (3, H) and peep.dtype == _f32, "lstmp_seq_backward"
+    fn = _lib().bigdl_lstmp_seq_bwd32 if f32 else _lib().bigdl_lstmp_seq_bwd
+    check(fn(ptr(gy), ptr(Ut), ptr(peep), ptr(acts), ptr(tcs), ptr(cs), ptr(c0), ptr(DG), ptr(gc), C.c_int(B),
+             C.c_int(T), C.c_int(H), _s()), "lstmp_seq_bwd")
+
+
+def lstmp_seq_backward(gy, Ut, peep, acts, tcs, cs, c0, DG, gc):
+    """LSTMPeephole BPTT: ``Ut`` [H][4H] = (U_i; U_f; U_g; U_o)ᵀ packed once per call; DG [B][T][4H]
+    gate gradients (i, f, g, o); gc [B][H] ← dc before the first step."""
+    _lstmp_seq_bwd(False, gy, Ut, peep, acts, tcs, cs, c0, DG, gc)
+
+
+def lstmp_seq_backward32(gy, Ut, peep, acts, tcs, cs, c0, DG, gc):
+    _lstmp_seq_bwd(True, gy, Ut, peep, acts, tcs, cs, c0, DG, gc)
+
+
+def peephole_grad(DG, cs, c0, gp_i, gp_f, gp_o, scale=1.0):
+    """gp_i += s·Σ DG_i∘c₋₁, gp_f += s·Σ DG_f∘c₋₁, gp_o += s·Σ DG_o∘c over all (b, t): the gradients of
+    LSTMPeephole's three CMul weights.  DG [B][T][4H] bf16 / fp32, cs fp32 [T][B][H], c0 [B][H] or
+    None, gp_* fp32 [H].  Row-chunk partials + one fold, no atomics: bit-reproducible."""
+    B, T, G = DG.shape
+    H = G // 4
+    assert _dense_bf16(DG, cs, c0) and H % 8 == 0 and tuple(cs.shape) == (T, B, H) and cs.dtype == _f32 \
+        and all(g.is_cuda and g.is_contiguous() and g.dtype == _f32 and g.numel() == H for g in (gp_i, gp_f, gp_o)) \
+        and DG.dtype in (_bf16, _f32), "peephole_grad"
+    part = torch.empty(((B * T + 31) // 32) * 3 * H, dtype=_f32, device=DG.device)
+    check(_lib().bigdl_peephole_grad(ptr(DG), C.c_int(1 if DG.dtype == _f32 else 0), ptr(cs), ptr(c0), ptr(gp_i),
+                                     ptr(gp_f), ptr(gp_o), _f(scale), ptr(part), _ll(part.numel()), C.c_int(B),
+                                     C.c_int(T), C.c_int(H), _s()), "peephole_grad")
 
 
 # ---------------------------------------------------------------------------------- K13 ClassNLL
