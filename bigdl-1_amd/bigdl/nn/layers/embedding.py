@@ -9,7 +9,7 @@ import torch
 from ... import ops
 from ..abstractnn import TensorModule
 from ...utils.table import Table
-from ...utils import acc_float
+from ...utils import acc_float, config
 
 DOUBLEMAX = 1.7976931348623157e308
 
@@ -98,7 +98,26 @@ class LookupTableSparse(TensorModule):
             rows, vals, w = rows[keep], vals[keep], w[keep]
         return n, rows, vals - 1, w
 
+    def _native_bag(self, input):
+        """(ids, rows, L, weights) for ``ops.embedding_bag_forward`` when the fused kernels serve this
+        input (``bigdl.embedding.nativeBag``, device tensors), else None.  Nothing is launched here
+        beyond the COO coalesce: the kernel takes the sorted rows or the dense ``n x L`` ids as they are."""
+        ids = input[1] if isinstance(input, Table) else input
+        wts = input[2] if isinstance(input, Table) and input.length() > 1 else None
+        if not (ids.is_cuda and config.get_property("bigdl.embedding.nativeBag")):
+            return None
+        if ids.is_sparse:
+            ids = ids.coalesce()
+            w = wts.coalesce().values().float() if wts is not None else None
+            return ids.values(), ids.indices()[0], ids.shape[0], w
+        return ids, None, ids.shape[1], (wts.float() if wts is not None else None)
+
     def updateOutput(self, input):
+        self._bag_state = None
+        bag = self._native_bag(input)
+        if bag is not None:
+            out, self._bag_state = ops.embedding_bag_forward(self.cw("weight"), *bag, self.combiner, self.maxNorm)
+            return out
         n, rows, cols, w = self._dense(input)
         emb = self.weight[cols]
         if self.maxNorm > 0:
@@ -117,6 +136,9 @@ class LookupTableSparse(TensorModule):
         return Table(torch.zeros(1), torch.zeros(1)) if isinstance(input, Table) else torch.zeros(1)
 
     def accGradParameters(self, input, gradOutput):
+        if getattr(self, "_bag_state", None) is not None:
+            ops.embedding_bag_backward(self.gradWeight, self._bag_state, gradOutput, self.cw("weight"), self.scale_w)
+            return
         n, rows, cols, w = self._cache
         g = gradOutput[rows] * w.unsqueeze(1)
         if self.combiner in ("mean", "sqrtn"):

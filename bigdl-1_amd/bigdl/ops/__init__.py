@@ -14,6 +14,7 @@ from .dispatch import native_status, native_has, __all__ as _dispatch_all  # noq
 from .dispatch import fallback_counts, reset_fallbacks  # noqa: F401
 from . import native_ops  # noqa: F401  (fused entry points beyond the dispatch table)
 from . import native  # noqa: F401
+from .native_ops import embedding_check  # noqa: F401
 
 __all__ = list(_dispatch_all) + ["reference", "native_status", "native_has", "native_ops", "native",
-                                 "fallback_counts", "reset_fallbacks"]
+                                 "fallback_counts", "reset_fallbacks", "embedding_check"]

@@ -12,6 +12,7 @@ static const char* kOps[] = {
     "rmsprop", "adadelta", "adamax", "ftrl", "adam_g16",
     "grad_sumsq", "sgd_clip", "optim_clip",
     "image_resample_norm",
+    "embedding_bag_fwd", "embedding_bag_bwd",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

@@ -19,6 +19,7 @@ __all__ = [
     "quant_rows", "gemm_i8", "image_crop_flip_norm", "attention_forward", "attention_backward",
     "attention_decode", "lars_sumsq", "lars_step", "grad_sumsq",
     "concat_forward", "concat_split_backward", "sum_n", "image_resample_norm",
+    "embedding_bag_forward", "embedding_bag_backward",
 ]
 
 

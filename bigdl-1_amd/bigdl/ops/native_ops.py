@@ -3137,6 +3137,92 @@ def embedding_backward(grad_weight, idx_1b, gy, scale=1.0, padding_value=0):
     return grad_weight
 
 
+_BAG_COMB = {"sum": 0, "mean": 1, "sqrtn": 2}
+
+
+@register("embedding_bag_forward")
+def embedding_bag_forward(weight, ids, rows, L, wts, combiner="sum", max_norm=-1.0):
+    """Combined embedding of ``n`` bags of 1-based ids (``csrc/embedding_bag.hip``).  ``rows`` is the
+    ascending int64 bag of every entry of a coalesced COO input (``L`` = the number of bags), or
+    None for a dense ``n x L`` input whose ids <= 0 are padding.  Returns ``(out [n, D] fp32, state)``;
+    ``state`` is what :func:`embedding_bag_backward` needs."""
+    if weight.dim() != 2 or weight.dtype not in (_bf16, _f32) or not weight.is_contiguous() or not _al16(weight):
+        return NotImplemented
+    if not ids.is_cuda or ids.dtype not in _ITYPE or combiner not in _BAG_COMB or ids.numel() == 0:
+        return NotImplemented
+    if rows is not None:
+        if rows.dtype != torch.int64 or rows.numel() != ids.numel() or ids.dim() != 1 or int(L) <= 0:
+            return NotImplemented
+        n, stride, rows = int(L), 0, rows.contiguous()
+    else:
+        if ids.dim() != 2:
+            return NotImplemented
+        n, stride = int(ids.shape[0]), int(ids.shape[1])
+    if wts is not None and (wts.dtype != _f32 or wts.numel() != ids.numel() or not wts.is_cuda):
+        return NotImplemented
+    nnz, D = ids.numel(), int(weight.shape[1])
+    if n >= 2 ** 31 or nnz >= 2 ** 31 or weight.shape[0] >= 2 ** 31 or D < 1:
+        return NotImplemented
+    ids_c = ids.contiguous()
+    wts_c = None if wts is None else wts.contiguous()
+    dev = weight.device
+    capturing = torch.cuda.is_current_stream_capturing()
+    st = _emb_state(dev)
+    if not capturing:
+        embedding_check(dev)
+    out = torch.empty((n, D), dtype=_f32, device=dev)
+    coef = torch.empty(nnz, dtype=_f32, device=dev)
+    inv2 = torch.empty(nnz, dtype=_f32, device=dev) if max_norm > 0 else None
+    check(_lib().bigdl_embedding_bag_fwd(ptr(weight), ptr(ids_c), C.c_int(_ITYPE[ids_c.dtype]), ptr(rows), ptr(wts_c),
+                                         ptr(out), ptr(coef), ptr(inv2), _ll(n), _ll(nnz), _ll(stride),
+                                         _ll(weight.shape[0]), C.c_int(D), C.c_int(0 if weight.dtype == _bf16 else 1),
+                                         C.c_int(_BAG_COMB[combiner]), _f(max_norm), ptr(st["flag"]), _s()),
+          "embedding_bag_fwd")
+    st["n_index"] = int(weight.shape[0])
+    if not capturing and st["event"] is None:
+        st["host"].copy_(st["flag"], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        st["event"] = ev
+        if config.get_property("bigdl.embedding.syncCheck"):
+            embedding_check(dev, sync=True)
+    return out, {"native": True, "ids": ids_c, "rows": rows, "L": stride, "n": n, "coef": coef, "inv2": inv2,
+                 "sort": None}
+
+
+@register("embedding_bag_backward")
+def embedding_bag_backward(grad_weight, state, gy, weight, scale=1.0):
+    """``grad_weight[r] += scale * d(out)/d(weight[r]) . gy`` for the forward that made ``state``, the
+    maxNorm clip term included; bitwise reproducible (segment sums over the stably sorted ids)."""
+    if not isinstance(state, dict) or not state.get("native"):
+        return NotImplemented
+    if grad_weight.dtype != _f32 or grad_weight.dim() != 2 or not grad_weight.is_contiguous() or not _al16(grad_weight):
+        return NotImplemented
+    if weight.shape != grad_weight.shape or weight.dtype not in (_bf16, _f32) or not weight.is_contiguous() \
+            or not _al16(weight):
+        return NotImplemented
+    n, D, ids = state["n"], int(grad_weight.shape[1]), state["ids"]
+    if gy.dtype not in (_bf16, _f32) or tuple(gy.shape) != (n, D) or not gy.is_cuda:
+        return NotImplemented
+    g = gy.contiguous()
+    if not _al16(g):
+        return NotImplemented
+    if scale == 0:
+        return grad_weight
+    if state["sort"] is None:
+        state["sort"] = torch.sort(ids.reshape(-1), stable=True)
+    sid, perm = state["sort"]
+    nnz = ids.numel()
+    part = torch.empty(((nnz + 31) // 32, 2, D), dtype=_f32, device=g.device)
+    check(_lib().bigdl_embedding_bag_bwd(ptr(grad_weight), ptr(weight), C.c_int(0 if weight.dtype == _bf16 else 1),
+                                         ptr(g), C.c_int(0 if g.dtype == _bf16 else 1), ptr(sid),
+                                         C.c_int(_ITYPE[sid.dtype]), ptr(perm), ptr(state["rows"]), ptr(state["coef"]),
+                                         ptr(state["inv2"]), ptr(part), _ll(n), _ll(nnz), _ll(state["L"]),
+                                         _ll(grad_weight.shape[0]), C.c_int(D), _f(scale), _s()),
+          "embedding_bag_bwd")
+    return grad_weight
+
+
 # ---------------------------------------------------------------------------------- K14/K15 fused recurrent step
 _RNN_CELLS = {"lstm_fwd": 0, "lstm_bwd": 1, "gru_fwd1": 2, "gru_fwd2": 3, "gru_bwd1": 4, "gru_bwd2": 5,
               "rnn_fwd": 6, "rnn_bwd": 7, "lstmp_fwd": 8, "lstmp_bwd": 9}

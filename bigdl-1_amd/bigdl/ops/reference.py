@@ -789,6 +789,46 @@ def embedding_backward(grad_weight, idx_1b, gy, scale=1.0, padding_value=0):
     grad_weight.index_add_(0, idx, g.to(grad_weight.dtype))
 
 
+def _bag_den(n, rows, w, combiner, dev):
+    den = torch.zeros(n, device=dev).index_add_(0, rows, w if combiner == "mean" else w * w)
+    return (den if combiner == "mean" else den.sqrt()).clamp_min(1e-12)
+
+
+def embedding_bag_forward(weight, ids, rows, L, wts, combiner="sum", max_norm=-1.0):
+    """``LookupTableSparse``'s torch form: ``rows`` = the bag of every entry of a coalesced COO input
+    (``L`` bags), or None for a dense ``n x L`` input whose ids <= 0 are padding."""
+    if rows is not None:
+        n, vals = int(L), ids.long()
+        w = wts.float() if wts is not None else torch.ones_like(vals, dtype=torch.float32)
+    else:
+        n = ids.shape[0]
+        rows = torch.arange(n, device=ids.device).repeat_interleave(ids.shape[1])
+        vals = ids.reshape(-1).long()
+        w = wts.reshape(-1).float() if wts is not None else torch.ones_like(vals, dtype=torch.float32)
+        keep = vals > 0
+        rows, vals, w = rows[keep], vals[keep], w[keep]
+    cols = vals - 1
+    emb = weight[cols].float()
+    if max_norm > 0:
+        nn_ = emb.norm(dim=1, keepdim=True)
+        emb = emb * torch.where(nn_ > max_norm, max_norm / nn_, torch.ones_like(nn_))
+    out = torch.zeros(n, weight.shape[1], device=emb.device)
+    out.index_add_(0, rows, emb * w.unsqueeze(1))
+    if combiner in ("mean", "sqrtn"):
+        out = out / _bag_den(n, rows, w, combiner, emb.device).unsqueeze(1)
+    return out, {"native": False, "n": n, "rows": rows, "cols": cols, "w": w, "combiner": combiner}
+
+
+def embedding_bag_backward(grad_weight, state, gy, weight, scale=1.0):
+    """The torch form's gradient (it leaves out the maxNorm clip term)."""
+    n, rows, cols, w = state["n"], state["rows"], state["cols"], state["w"]
+    g = gy.float()[rows] * w.unsqueeze(1)
+    if state["combiner"] in ("mean", "sqrtn"):
+        g = g / _bag_den(n, rows, w, state["combiner"], g.device)[rows].unsqueeze(1)
+    grad_weight.index_add_(0, cols, g * scale)
+    return grad_weight
+
+
 def dropout_forward(x, p, generator=None):
     """``DL/nn/Dropout.scala:64-150``: drop with probability p, scale kept values by 1/(1-p)."""
     if p <= 0:
