@@ -20,7 +20,16 @@ Design (MI355X-first, not the reference's clone-a-cell-per-step scheme):
   one-launch-per-step kernels (rnn_step.hip cells 6-9) with explicit BPTT; the peephole cell's four
   ``h2g`` weights are read in place, its CMul gradients come from one column-reduction kernel.
   ``bigdl.rnn.nativeCells=false`` sends these two cells back to the generic path.
-* Every other cell (GRU with dropout, ConvLSTM, MultiRNNCell, custom cells) declares a
+* **ConvLSTMPeephole fast path** (2-D cell, stride 1, same padding, odd kernels, ``outputSize % 8 == 0``,
+  default Tanh/Sigmoid, bf16 on a GPU): the four input convolutions of all T steps are ONE native
+  convolution over the T·B images with 4·C stacked output channels; the recurrence runs one fused
+  launch per step (convlstm.hip: implicit-GEMM recurrent convolution on MFMA with the gate, peephole
+  and cell math on its accumulators), forward and explicit BPTT.  The hidden sequence is stored
+  time-major and pixel-major ([T+1][B][H][W][C], h0 in slot 0) and the (B, T, C, H, W) output is a
+  permuted view of it, so the weight gradients of the input and of the recurrent convolutions are
+  each ONE native backward over T·B images after the loop.  ``bigdl.rnn.nativeConvLSTM=false`` restores
+  the generic path.
+* Every other cell (GRU with dropout, ConvLSTM3D or ConvLSTM outside the above, MultiRNNCell, custom cells) declares a
   differentiable ``step(x, hidden, tape)`` on torch device ops; the time loop is recorded once
   and BPTT is a single autograd pass.  Parameters enter through a ``_Tape`` that hands out
   compute-dtype leaves, fires the owning modules' pre-forward hooks (the DistriOptimizer's
@@ -868,6 +877,21 @@ class Recurrent(Container):
             return False
         return _native_cell_operands_ok(c.hiddenSize, x2, *[l.cw("weight") for l in c.h2g])
 
+    def _use_fast_convlstm(self, x2):
+        c = self.topology
+        if not (self.fast_lstm and type(c) is ConvLSTMPeephole and not self.maskZero and x2.dim() == 5
+                and bool(config.get_property("bigdl.rnn.nativeConvLSTM"))):
+            return False
+        if not (c.stride == 1 and c.padding == -1 and c.kernelC % 2 == 1 and c.kernelI % 2 == 1
+                and c.outputSize % 8 == 0 and x2.shape[2] == c.inputSize
+                and _is_default(c.activation, Tanh) and _is_default(c.innerActivation, Sigmoid)):
+            return False
+        if not (x2.is_cuda and x2.dtype == torch.bfloat16 and _cdtype(x2) == torch.bfloat16):
+            return False
+        from ...ops import native_ops as NO
+        return (NO.N.has("conv2d_forward") and NO.convlstm_ok(c.outputSize, c.kernelC)
+                and all(m.cw("weight").dtype == torch.bfloat16 for m in c.gh))
+
     # -- stacked-LSTM fusion (bigdl.nn.fusion ``lstmstack``) ----------------------------------
     #: lower layer: the next Recurrent(LSTM) whose only input is this layer's output; upper layer:
     #: the layer feeding it.  The pair then runs on the layer wavefront (rnn_step.hip
@@ -916,6 +940,8 @@ class Recurrent(Container):
             return self._rnn_forward(x2)
         if self._use_fast_peephole(x2):
             return self._lstmp_forward(x2)
+        if self._use_fast_convlstm(x2):
+            return self._convlstm_forward(x2)
         return self._generic_forward(input, x2)
 
     def _lstm_forward(self, x2):
@@ -1093,6 +1119,51 @@ class Recurrent(Container):
         self._rec = ("lstmp", h0, c0, out, acts, tcs, cs, peep) if train else None
         return out
 
+    def _convlstm_forward(self, x2):
+        """ConvLSTMPeephole: one input convolution over all T·B images, then one fused launch per step
+        (convlstm.hip).  Everything is time-major NHWC; the output is a view of the hidden sequence."""
+        from ...ops import native_ops as NO
+        cell: ConvLSTMPeephole = self.topology
+        B, Tn, Cin, H, W = x2.shape
+        Ch, kC, kI = cell.outputSize, cell.kernelC, cell.kernelI
+        dev, bf = x2.device, torch.bfloat16
+        train = self.train
+        _fire_pre_forward(cell.gx + cell.gh + cell.peep)
+        ws = [NO._krsc(m._w4(m.cw("weight"))) for m in cell.gh]  # [C][kC][kC][C], read where they lie
+        ws = [w if w.data_ptr() % 16 == 0 else w.clone() for w in ws]  # (a 16-byte-misaligned arena view: copied)
+        peep = (torch.stack([m.weight.detach().reshape(Ch).to(torch.float32) for m in cell.peep])
+                if cell.withPeephole else None)
+        # everything the backward needs from the weights is prepared here, before the input convolution
+        wt = NO.convlstm_bwd_weights(ws) if train else None
+        Wh = torch.cat(ws, 0).permute(0, 3, 1, 2) if train else None
+        Wx = torch.cat([NO._krsc(m._w4(m.cw("weight"))) for m in cell.gx], 0).permute(0, 3, 1, 2)  # (4C, Cin, kI, kI)
+        bx = torch.cat([m.bias.detach().to(torch.float32) for m in cell.gx])
+        hs = torch.empty(Tn + 1, B, H, W, Ch, device=dev, dtype=bf)
+        if self._init_hidden_state is not None:
+            h0, c0 = self._h0(B, [Ch, H, W], dev, bf)
+            hs[0].copy_(h0.permute(0, 2, 3, 1))
+            c0 = acc_float(c0).to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        else:
+            hs[0].zero_()
+            c0 = None  # the kernels take a null c_{-1} as zero
+        xin = x2.permute(1, 0, 3, 4, 2).contiguous().view(Tn * B, H, W, Cin).permute(0, 3, 1, 2)
+        pad = ((kI - 1) // 2, (kI - 1) // 2)
+        gx = ops.conv2d_forward(xin, Wx, bx, (1, 1), pad)  # counted by note_fallback when the native conv declines
+        gx = gx.to(bf).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)  # [T·B][H][W][4C]
+        if train:
+            acts = torch.empty(Tn, B, H, W, 4 * Ch, device=dev, dtype=torch.float32)
+            tcs = torch.empty(Tn, B, H, W, Ch, device=dev, dtype=torch.float32)
+            cs = torch.empty(Tn, B, H, W, Ch, device=dev, dtype=torch.float32)
+            cbuf = None
+        else:
+            acts = tcs = cs = None
+            cbuf = torch.empty(2, B, H, W, Ch, device=dev, dtype=torch.float32)
+        NO.convlstm_seq_forward(hs, gx, c0, ws, peep, cs, acts, tcs, cbuf)
+        c_last = cs[Tn - 1] if train else cbuf[(Tn - 1) % 2]
+        self._last_hidden = T(hs[Tn].permute(0, 3, 1, 2), c_last.permute(0, 3, 1, 2))
+        self._rec = ("convlstm", xin, hs, c0, acts, tcs, cs, peep, wt, Wh, Wx) if train else None
+        return hs[1:].permute(1, 0, 4, 2, 3)
+
     def _generic_forward(self, input, x2):
         cell = self.topology
         B, Tn = x2.shape[0], x2.shape[1]
@@ -1149,6 +1220,8 @@ class Recurrent(Container):
             return self._rnn_backward(gradOutput)
         if rec[0] == "lstmp":
             return self._lstmp_backward(gradOutput)
+        if rec[0] == "convlstm":
+            return self._convlstm_backward(gradOutput)
         _, tape, xl, flat0, out = rec
         targets = ([xl] if xl.requires_grad else []) + flat0 + tape.param_leaves()
         grads = torch.autograd.grad([out], targets, [gradOutput.to(out.dtype)], allow_unused=True)
@@ -1322,6 +1395,76 @@ class Recurrent(Container):
         _fire_grad_ready(cell.h2g + cell.peep)
         self._rec = None
         return DG
+
+    def _convlstm_backward(self, gradOutput):
+        """BPTT on one fused launch per step, then ONE native conv backward each for the recurrent
+        weights (x = [h0, h_1 .. h_{T-1}], slots 0..T-1 of the hidden sequence) and for the input
+        convolution (input gradient, weights, biases), both with DG as the 4·C-channel output gradient.
+        The four layers' gradient tensors are not adjacent in the arena, so each backward accumulates
+        into one fp32 scratch whose four slices are added with the layers' scales."""
+        from ...ops import native_ops as NO
+        _, xin, hs, c0, acts, tcs, cs, peep, wt, Wh, Wx = self._rec
+        cell: ConvLSTMPeephole = self.topology
+        T1, B, H, W, Ch = hs.shape
+        Tn, kC, kI = T1 - 1, cell.kernelC, cell.kernelI
+        dev = hs.device
+        gy = gradOutput.permute(1, 0, 3, 4, 2).to(dtype=hs.dtype, memory_format=torch.contiguous_format)
+        DG = torch.empty(Tn, B, H, W, 4 * Ch, device=dev, dtype=hs.dtype)  # (di', df', do', dg') per step
+        gc = torch.empty(B, H, W, Ch, device=dev, dtype=torch.float32)
+        dh0 = torch.empty(B, H, W, Ch, device=dev, dtype=torch.float32)
+        NO.convlstm_seq_backward(gy, wt, peep, acts, tcs, cs, c0, DG, gc, dh0)
+        self._grad_hidden_state = [dh0.permute(0, 3, 1, 2), gc.permute(0, 3, 1, 2)]
+        dgn = DG.view(Tn * B, H, W, 4 * Ch).permute(0, 3, 1, 2)
+
+        def scratch(k, cin):
+            t = torch.empty(4 * Ch, k, k, cin, device=dev, dtype=torch.float32)
+            if NO.zero_fill(t) is NotImplemented:
+                t.zero_()
+            return t.permute(0, 3, 1, 2)
+
+        gwh = scratch(kC, Ch) if any(m.scale_w != 0 for m in cell.gh) else None
+        if gwh is not None:
+            hprev = hs[:Tn].view(Tn * B, H, W, Ch).permute(0, 3, 1, 2)
+            ops.conv2d_backward(dgn, hprev, Wh, (1, 1), ((kC - 1) // 2, (kC - 1) // 2), (1, 1), 1, False, gwh, None, 1.0)
+        gwx = scratch(kI, xin.shape[1]) if any(m.scale_w != 0 for m in cell.gx) else None
+        gbx = None
+        if any(m.scale_b != 0 for m in cell.gx):
+            gbx = torch.empty(4 * Ch, device=dev, dtype=torch.float32)
+            if NO.zero_fill(gbx) is NotImplemented:
+                gbx.zero_()
+            if NO.colsum_acc(DG.view(-1, 4 * Ch), gbx) is NotImplemented:
+                raise RuntimeError("ConvLSTM input bias gradient: no native column sum for these rows")
+        gi = ops.conv2d_backward(dgn, xin, Wx, (1, 1), ((kI - 1) // 2, (kI - 1) // 2), (1, 1), 1, True, gwx, None, 1.0)
+        NO.join_wgrad()  # the scratch slices are read on this stream
+        for k in range(4):
+            mh, mx = cell.gh[k], cell.gx[k]
+            sl = slice(k * Ch, (k + 1) * Ch)
+            if mh.scale_w != 0:
+                mh.gradWeight.add_(gwh[sl].reshape(mh.gradWeight.shape), alpha=mh.scale_w)
+                if mh.wRegularizer is not None:
+                    mh.wRegularizer.accRegularization(mh.weight, mh.gradWeight, mh.scale_w)
+            if mx.scale_w != 0:
+                mx.gradWeight.add_(gwx[sl].reshape(mx.gradWeight.shape), alpha=mx.scale_w)
+                if mx.wRegularizer is not None:
+                    mx.wRegularizer.accRegularization(mx.weight, mx.gradWeight, mx.scale_w)
+            if mx.scale_b != 0:
+                mx.gradBias.add_(gbx[sl], alpha=mx.scale_b)
+                if mx.bRegularizer is not None:
+                    mx.bRegularizer.accRegularization(mx.bias, mx.gradBias, mx.scale_b)
+        if cell.withPeephole and any(m.scale_w != 0 for m in cell.peep):
+            gp = torch.empty(3, Ch, device=dev, dtype=torch.float32)
+            if NO.zero_fill(gp) is NotImplemented:
+                gp.zero_()
+            NO.convlstm_peephole_grad(DG, cs, c0, gp)
+            for m, g in zip(cell.peep, gp):
+                if m.scale_w != 0:
+                    m.gradWeight.add_(g.reshape(m.gradWeight.shape), alpha=m.scale_w)
+                    if m.wRegularizer is not None:
+                        m.wRegularizer.accRegularization(m.weight, m.gradWeight, m.scale_w)
+        _fire_grad_ready(cell.gx + cell.gh + cell.peep)
+        self._rec = None
+        B_, Cin = B, xin.shape[1]
+        return gi.permute(0, 2, 3, 1).reshape(Tn, B_, H, W, Cin).permute(1, 0, 4, 2, 3)
 
     def _stacked_upper(self):
         return self._rec is not None and self._rec[0] == "lstm2"

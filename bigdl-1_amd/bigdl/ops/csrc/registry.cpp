@@ -13,6 +13,7 @@ static const char* kOps[] = {
     "grad_sumsq", "sgd_clip", "optim_clip",
     "image_resample_norm",
     "embedding_bag_fwd", "embedding_bag_bwd",
+    "convlstm_step", "convlstm_seq_fwd", "convlstm_seq_bwd", "convlstm_peephole_grad",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

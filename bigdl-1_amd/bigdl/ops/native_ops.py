@@ -3518,6 +3518,103 @@ def peephole_grad(DG, cs, c0, gp_i, gp_f, gp_o, scale=1.0):
                                      C.c_int(T), C.c_int(H), _s()), "peephole_grad")
 
 
+# ---------------------------------------------------------------------------------- ConvLSTMPeephole (convlstm.hip)
+def _convlstm_ok(B, H, W, C_, kC, bf16=(), f32=()):
+    """The operand contract of the ConvLSTM step kernels, in one place: C % 8 == 0, odd kC whose halo
+    and weight ring fit in LDS, dense 16-byte-aligned device tensors of the right type (``None`` =
+    absent), every one ≤ 2³¹ elements per step."""
+    if not (B > 0 and H > 0 and W > 0 and C_ > 0 and C_ % 8 == 0 and kC % 2 == 1 and B <= 65535):
+        return False
+    l = _lib()
+    if l is None or not hasattr(l, "bigdl_convlstm_lds_bytes"):
+        return False
+    l.bigdl_convlstm_lds_bytes.restype = C.c_longlong
+    if not 0 < l.bigdl_convlstm_lds_bytes(C.c_int(C_), C.c_int(kC)) <= 65536:
+        return False
+    return _dense_bf16(*bf16, *f32) and all(t is None or t.dtype == _bf16 for t in bf16) \
+        and all(t is None or t.dtype == _f32 for t in f32)
+
+
+def convlstm_ok(C_, kC) -> bool:
+    """Eligibility of a cell's geometry (channel count, recurrent kernel size) for the step kernels."""
+    return _convlstm_ok(1, 1, 1, C_, kC)
+
+
+def convlstm_step(mode, a, w, B, H, W, C_, kC, gx=None, c_prev=None, peep=None, h_out=None, c_out=None, act=None,
+                  tc=None, gy=None, dc_next=None, dg=None, dc_prev=None):
+    """One ConvLSTMPeephole step.  ``mode`` "fwd": ``a`` = h_{t-1} [B][H][W][C] (None = 0), ``w`` the four
+    recurrent weights (i, f, o, g), each [C][kC][kC][C]; gx [B][H][W][4C]; writes h_out (bf16), c_out, act
+    [..][4C] (i, f, o, g), tc (fp32, optional).  "bwd": ``a`` = DG_{t+1} [B][H][W][4C] (None = last step),
+    ``w`` the transformed blocks [4][C][kC][kC][C] (:func:`convlstm_bwd_weights`); reads gy, act, tc,
+    c_prev, dc_next (None = 0); writes dg [..][4C] and dc_prev.  ``peep`` fp32 [3][C] or None."""
+    fwd = mode == "fwd"
+    ws = list(w) if fwd else [w, None, None, None]
+    n = B * H * W
+    shapes = [(a, n * (C_ if fwd else 4 * C_)), (gx, 4 * n * C_), (c_prev, n * C_), (peep, 3 * C_), (h_out, n * C_),
+              (c_out, n * C_), (act, 4 * n * C_), (tc, n * C_), (gy, n * C_), (dc_next, n * C_), (dg, 4 * n * C_),
+              (dc_prev, n * C_)] + [(x, (1 if fwd else 4) * C_ * kC * kC * C_) for x in ws]
+    assert _convlstm_ok(B, H, W, C_, kC, (a, gx, h_out, gy, dg, *ws), (c_prev, peep, c_out, act, tc, dc_next, dc_prev)) \
+        and all(t is None or t.numel() == k for t, k in shapes), "convlstm_step"
+    check(_lib().bigdl_convlstm_step(C.c_int(0 if fwd else 1), ptr(a), *[ptr(x) for x in ws], ptr(gx), ptr(c_prev),
+                                     ptr(peep), ptr(h_out), ptr(c_out), ptr(act), ptr(tc), ptr(gy), ptr(dc_next),
+                                     ptr(dg), ptr(dc_prev), C.c_int(B), C.c_int(H), C.c_int(W), C.c_int(C_),
+                                     C.c_int(kC), _s()), f"convlstm_step[{mode}]")
+
+
+def convlstm_bwd_weights(ws):
+    """The four recurrent weights [C_out][kC][kC][C_in] → [4][C_in][kC][kC][C_out] with both tap axes
+    flipped: the operand of the backward step's dh = Σ_k DG_k ⊛ flip(Wh_k)ᵀ (once per sequence)."""
+    return torch.stack([w.flip(1, 2).permute(3, 1, 2, 0) for w in ws]).contiguous()
+
+
+def convlstm_seq_forward(hs, gx, c0, ws, peep, cs, acts, tcs, cbuf):
+    """Whole-sequence forward (bigdl_convlstm_seq_fwd).  hs [T+1][B][H][W][C] bf16 with h0 in slot 0 (steps
+    fill slots 1..T); gx [T][B][H][W][4C] bf16 (i, f, o, g); c0 fp32 [B][H][W][C] or None; training saves cs /
+    tcs [T][B][H][W][C] and acts [T][B][H][W][4C] (fp32); inference (cs None) ping-pongs c through cbuf
+    [2][B][H][W][C]."""
+    T1, B, H, W, C_ = hs.shape
+    T, kC = T1 - 1, ws[0].shape[1]
+    n = B * H * W * C_
+    assert T >= 1 and _convlstm_ok(B, H, W, C_, kC, (hs, gx, *ws), (c0, peep, cs, acts, tcs, cbuf)) and len(ws) == 4 \
+        and all(tuple(w.shape) == (C_, kC, kC, C_) for w in ws) and gx.numel() == 4 * T * n \
+        and (c0 is None or c0.numel() == n) and (peep is None or peep.numel() == 3 * C_) \
+        and ((cs.numel() == T * n and tcs.numel() == T * n and acts.numel() == 4 * T * n) if cs is not None
+             else cbuf.numel() == 2 * n), "convlstm_seq_forward"
+    check(_lib().bigdl_convlstm_seq_fwd(ptr(hs), ptr(gx), ptr(c0), *[ptr(w) for w in ws], ptr(peep), ptr(cs), ptr(acts),
+                                        ptr(tcs), ptr(cbuf), C.c_int(B), C.c_int(T), C.c_int(H), C.c_int(W),
+                                        C.c_int(C_), C.c_int(kC), _s()), "convlstm_seq_fwd")
+
+
+def convlstm_seq_backward(gy, wt, peep, acts, tcs, cs, c0, DG, gc, dh0=None):
+    """BPTT (bigdl_convlstm_seq_bwd).  gy [T][B][H][W][C] bf16; ``wt`` from :func:`convlstm_bwd_weights`; DG
+    [T][B][H][W][4C] bf16 ← gate gradients (i, f, o, g); gc fp32 [B][H][W][C] ← dc before the first step; dh0
+    (optional, fp32 [B][H][W][C]) ← the initial hidden state's gradient."""
+    T, B, H, W, C_ = gy.shape
+    kC = wt.shape[2]
+    n = B * H * W * C_
+    assert _convlstm_ok(B, H, W, C_, kC, (gy, wt, DG), (peep, acts, tcs, cs, c0, gc, dh0)) \
+        and tuple(wt.shape) == (4, C_, kC, kC, C_) and DG.numel() == 4 * T * n and acts.numel() == 4 * T * n \
+        and tcs.numel() == T * n and cs.numel() == T * n and gc.numel() == n and (c0 is None or c0.numel() == n) \
+        and (dh0 is None or dh0.numel() == n) and (peep is None or peep.numel() == 3 * C_), "convlstm_seq_backward"
+    check(_lib().bigdl_convlstm_seq_bwd(ptr(gy), ptr(wt), ptr(peep), ptr(acts), ptr(tcs), ptr(cs), ptr(c0), ptr(DG),
+                                        ptr(gc), ptr(dh0), C.c_int(B), C.c_int(T), C.c_int(H), C.c_int(W),
+                                        C.c_int(C_), C.c_int(kC), _s()), "convlstm_seq_bwd")
+
+
+def convlstm_peephole_grad(DG, cs, c0, gp, scale=1.0):
+    """gp[0] += s·Σ DG_i∘c₋₁, gp[1] += s·Σ DG_f∘c₋₁, gp[2] += s·Σ DG_o∘c over every (t, b, y, x): DG
+    [T][B][H][W][4C] bf16 (i, f, o, g), cs fp32 [T][B][H][W][C], c0 [B][H][W][C] or None, gp fp32 [3][C].
+    Row-chunk partials + one fold in index order, no atomics: bit-reproducible."""
+    T, B, H, W, C_ = cs.shape
+    n, np_ = T * B * H * W, B * H * W
+    assert _convlstm_ok(B, H, W, C_, 1, (DG,), (cs, c0, gp)) and DG.numel() == 4 * n * C_ and gp.numel() == 3 * C_ \
+        and (c0 is None or c0.numel() == np_ * C_), "convlstm_peephole_grad"
+    part = torch.empty(((n + 255) // 256) * 3 * C_, dtype=_f32, device=DG.device)
+    check(_lib().bigdl_convlstm_peephole_grad(ptr(DG), ptr(cs), ptr(c0), ptr(gp), _f(scale), ptr(part),
+                                              _ll(part.numel()), _ll(n), _ll(np_), C.c_int(C_), _s()),
+          "convlstm_peephole_grad")
+
+
 # ---------------------------------------------------------------------------------- K13 ClassNLL
 def _nll_args(logp, target_1b, weights):
     lp = logp.unsqueeze(0) if logp.dim() == 1 else logp

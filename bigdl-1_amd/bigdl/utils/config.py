@@ -57,6 +57,7 @@ _REGISTRY = {
     "bigdl.bn.syncOneRankLocal": (bool, True, "a SyncBN whose sync group has ONE rank (also the forced world-size-1 rehearsal) runs the local BN kernels: the all-reduce is the identity there, so the compaction of the statistics replicas and the one-launch global finalize+apply are skipped; False rehearses the multi-rank kernels at one rank"),
     "bigdl.bn.shiftedStats": (bool, True, "conv-epilogue BN statistics as Σ(y−K), Σ(y−K)² with K = the BN running mean"),
     "bigdl.rnn.nativeCells": (bool, True, "Recurrent(RnnCell) / Recurrent(LSTMPeephole) on a GPU run the fused step kernels (rnn_step.hip cells 6-9) with explicit BPTT; false = the generic per-step autograd path"),
+    "bigdl.rnn.nativeConvLSTM": (bool, True, "Recurrent(ConvLSTMPeephole) (2-D, stride 1, same padding, default activations, bf16 on a GPU) runs the fused conv-recurrent step kernels (convlstm.hip) with explicit BPTT; false = the generic per-step autograd path"),
     "bigdl.checkpoint.async": (bool, True, "trigger-driven checkpoints: host snapshot on the training thread, serialise + write on a writer thread"),
     "bigdl.predict.compiled": (bool, True, "LocalPredictor / Predictor / PredictionService on a GPU: lower the model through the IR (BN fold, conv+sum+ReLU), plan each batch shape once and replay its forward as a HIP graph (the reference's predictors always convert, LocalPredictor.scala:66)"),
     "bigdl.compile.lower": (bool, True, "nn.compiled.compile (inference phase): lower the model through the IR first (utils/intermediate.ConversionUtils: BN folded into convs / Linears, conv+sum+ReLU epilogues)"),
