@@ -201,11 +201,87 @@ class BinaryTreeLSTM(TreeLSTM):
             Hs = Hs.index_copy(0, me, h)
         return Hs.view(B, N, H)
 
+    # ---- native path: ops/csrc/treelstm.hip, one fused gather-GEMM-gate launch per tree level --------
+    def _nat_plan(self, input):
+        """The host plan of this batch when the level kernels serve it, else None.  On a device every
+        other case is noted as a fallback of ``treelstm_forward`` (``bigdl.native.strict`` raises)."""
+        x, trees = input[1], input[2]
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            return None
+        from ...ops import native as N, native_ops as NO
+        from ...utils import config
+        from ...utils.engine import Engine
+        H, G = self.hiddenSize, self._G
+        why = None
+        if not config.get_property("bigdl.treelstm.native") or not N.has("treelstm_forward"):
+            why = "disabled"
+        elif Engine.compute_dtype() != torch.bfloat16 or not x.is_floating_point() or x.dtype == torch.float64:
+            why = "dtype"
+        elif x.dim() != 3 or x.shape[2] != self.inputSize or not NO.treelstm_ok(H, self.inputSize, G):
+            why = "size"
+        plan = None if why else NO.treelstm_plan(trees, x.shape[1], x.device)
+        if plan is None:
+            N.note_fallback("treelstm_forward", why or "tree", (x,))
+        return plan
+
+    def _nat_pack(self):
+        from ...ops import native_ops as NO
+        bf = torch.bfloat16
+        names = ["left", "right", "leaf_c"] + (["leaf_o"] if self.gateOutput else [])
+        return NO.treelstm_pack(self.hiddenSize, self.inputSize,
+                                *[self.cw(f"{n}_weight", bf).contiguous() for n in names[:2]],
+                                *[getattr(self, f"{n}_bias").float().contiguous() for n in names[:2]],
+                                *[t for n in names[2:] for t in (self.cw(f"{n}_weight", bf).contiguous(),
+                                                                  getattr(self, f"{n}_bias").float().contiguous())])
+
+    def updateOutput(self, input):
+        self._nat = None
+        plan = self._nat_plan(input)
+        if plan is None:
+            return super().updateOutput(input)
+        from ...ops import native_ops as NO
+        x = input[1]
+        B, L, _ = x.shape
+        pack = self._nat_pack()
+        h, st = NO.treelstm_forward(x.reshape(B * L, -1).to(torch.bfloat16).contiguous(), plan, pack, self.train)
+        if self.train:
+            self._nat = (id(input), st, pack)
+        self._gi_done = False
+        return h.view(B, plan["N"], self.hiddenSize).to(x.dtype)
+
+    def _nat_backward(self, input, gradOutput, need_input):
+        from ...ops import native_ops as NO
+        _, st, pack = self._nat
+        self._nat = None
+        x, s = input[1], self.scale_w
+        grads = {w: getattr(self, g) for w, g in self._param_slots}
+        gy = gradOutput.reshape(-1, self.hiddenSize).to(torch.bfloat16).contiguous()
+        gx = NO.treelstm_backward(gy, st, pack, grads if s != 0 else None, s, need_input)
+        if self.wRegularizer is not None and s != 0:
+            for w, g in self._param_slots:
+                self.wRegularizer.accRegularization(getattr(self, w), getattr(self, g), s)
+        self._gi_done = True
+        if gx is None:
+            return None
+        return Table(gx.reshape(x.shape).to(x.dtype), torch.zeros_like(input[2]))
+
     def updateGradInput(self, input, gradOutput):
+        if getattr(self, "_nat", None) is not None and self._nat[0] == id(input):
+            return self._nat_backward(input, gradOutput, True)
         gi = super().updateGradInput(input, gradOutput)
         if isinstance(gi, Table) and gi.get(2) is None:
             gi[2] = torch.zeros_like(input[2])
         return gi
+
+    def accGradParameters(self, input, gradOutput):
+        if getattr(self, "_gi_done", False):
+            self._gi_done = False
+            return
+        if getattr(self, "_nat", None) is not None and self._nat[0] == id(input):
+            self._nat_backward(input, gradOutput, False)
+            self._gi_done = False
+            return
+        super().accGradParameters(input, gradOutput)
 
     def __repr__(self):
         return f"{self.get_name()}({self.inputSize}, {self.hiddenSize}, gateOutput={self.gateOutput})"

@@ -14,6 +14,7 @@ static const char* kOps[] = {
     "image_resample_norm",
     "embedding_bag_fwd", "embedding_bag_bwd",
     "convlstm_step", "convlstm_seq_fwd", "convlstm_seq_bwd", "convlstm_peephole_grad",
+    "treelstm_level", "treelstm_fwd", "treelstm_bwd", "treelstm_pack",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

@@ -3615,6 +3615,232 @@ def convlstm_peephole_grad(DG, cs, c0, gp, scale=1.0):
           "convlstm_peephole_grad")
 
 
+# ---------------------------------------------------------------------------------- BinaryTreeLSTM (treelstm.hip)
+def _up(n, m):
+    return (n + m - 1) // m * m
+
+
+def treelstm_ok(H, in_, G) -> bool:
+    """True when the level kernels take hidden size ``H`` / input size ``in_`` with ``G`` composer gates (even
+    sizes; LDS within the 64 KB limit)."""
+    l = _lib()
+    if l is None or not hasattr(l, "bigdl_treelstm_lds_bytes"):
+        return False
+    l.bigdl_treelstm_lds_bytes.restype = C.c_longlong
+    return 0 < l.bigdl_treelstm_lds_bytes(C.c_int(H), C.c_int(in_), C.c_int(G)) <= 65536
+
+
+def treelstm_plan(trees, L, device):
+    """Host plan of a batch of binary trees ``(B, N, 3)`` (TensorTree rows) over ``L`` embedding rows per tree,
+    uploaded in one transfer as int32 ``[5][R]``: node, left child, right child (flat ids ``b·N + i − 1``), the
+    parent's row among the composer rows (−1: a root) and the side (0 left, 1 right).  Rows ``[0, R0)`` are the
+    leaf row space ``b·L + leaf − 1`` padded to 32 (node −1 where no node uses the embedding row); then one
+    block of rows per height, left children first, each side padded to whole 32-row tiles.  Returns None for
+    anything the level kernels do not take: a node that is not binary, a child of two parents or of none that
+    exists, a cycle, two leaves on one embedding row."""
+    import numpy as np
+    t = trees.detach().to("cpu").numpy().astype(np.int64)
+    if t.ndim != 3 or t.shape[2] != 3 or t.size == 0:
+        return None
+    B, N, _ = t.shape
+    first, second, leafno = t[..., 0], t[..., 1], t[..., 2]
+    comp, leaf = first > 0, first == 0
+    if (comp & (second <= 0)).any() or (t[..., :2] > N).any() or (first < -1).any() or B * N >= 2 ** 31 // 2 \
+            or (leaf & ((leafno < 1) | (leafno > L))).any():
+        return None
+    base = (np.arange(B) * N)[:, None]
+    lch = np.where(comp, base + first - 1, -1).reshape(-1)
+    rch = np.where(comp, base + second - 1, -1).reshape(-1)
+    compf, leaff = comp.reshape(-1), leaf.reshape(-1)
+    height = np.where(leaff, 0, -1)
+    todo = compf.copy()
+    while todo.any():   # one sweep per tree height, all trees at once
+        idx = np.nonzero(todo)[0]
+        hl, hr = height[lch[idx]], height[rch[idx]]
+        ready = (hl >= 0) & (hr >= 0)
+        if not ready.any():
+            return None
+        height[idx[ready]] = 1 + np.maximum(hl, hr)[ready]
+        todo[idx[ready]] = False
+    ci = np.nonzero(compf)[0]
+    kids = np.concatenate([lch[ci], rch[ci]])
+    if kids.size and np.bincount(kids).max() > 1:
+        return None
+    parent, side = np.full(B * N, -1), np.zeros(B * N, dtype=np.int64)
+    parent[lch[ci]], parent[rch[ci]], side[rch[ci]] = ci, ci, 1
+    li = np.nonzero(leaff)[0]
+    lrow = (li // N) * L + leafno.reshape(-1)[li] - 1
+    if li.size and np.bincount(lrow).max() > 1:
+        return None
+    R0 = _up(B * L, 32)
+    rowof = np.full(B * N, -1)
+    rowof[li] = lrow
+    blocks, lvl, off = [np.full(R0, -1)], [R0], R0
+    blocks[0][lrow] = li
+    for hgt in range(1, int(height.max(initial=0)) + 1):
+        ids = np.nonzero(height == hgt)[0]
+        lv = np.concatenate([np.concatenate([g, np.full(_up(g.size, 32) - g.size, -1)])
+                             for g in (ids[side[ids] == 0], ids[side[ids] == 1])])
+        rowof[lv[lv >= 0]] = off + np.nonzero(lv >= 0)[0]
+        blocks.append(lv)
+        lvl.append(int(lv.size))
+        off += lv.size
+    node = np.concatenate(blocks)
+    v = node >= 0
+    nz = np.where(v, node, 0)
+    plan = np.stack([node, np.where(v, lch[nz], -1), np.where(v, rch[nz], -1),
+                     np.where(v & (parent[nz] >= 0), rowof[parent[nz]] - R0, -1), np.where(v, side[nz], 0)])
+    return {"plan": torch.from_numpy(plan.astype(np.int32)).to(device), "lvl": lvl, "R": int(node.size), "R0": R0,
+            "B": B, "N": N, "L": L}
+
+
+def _tl_mat(t, dtype, al=True):
+    """None or a dense device tensor of ``dtype``; the level kernels want 16-byte bases, the pack and
+    accumulate kernels read and write scalars (parameters may be views into a flat arena)."""
+    return t is None or (t.is_cuda and t.dtype == dtype and t.is_contiguous() and (not al or _al16(t)))
+
+
+def treelstm_pack(H, in_, left_w, right_w, left_b, right_b, leaf_c_w, leaf_c_b, leaf_o_w=None, leaf_o_b=None):
+    """The level kernels' weight forms from the bf16 parameters and fp32 biases (k_treelstm_pack, four
+    launches): ``wc`` / ``bc`` composer forward [G][H16][Wl | Wr, halves padded to 32] with bias bl + br, ``wl`` /
+    ``bl`` leaf forward [(c, o)][H16][in padded to 32], ``wt`` composer backward [side][H16][G·H8 padded to 32]
+    and ``wlt`` the transposed leaf weights [in8][(c, o)·H8] (the B operand of the embedding gradient)."""
+    go = leaf_o_w is not None
+    G, GL, Hp, H16 = (5 if go else 4), (2 if go else 1), _up(H, 8), _up(H, 16)
+    ws, bs = (left_w, right_w, leaf_c_w, leaf_o_w), (left_b, right_b, leaf_c_b, leaf_o_b)
+    assert treelstm_ok(H, in_, G) and all(_tl_mat(w, _bf16, False) for w in ws) and all(_tl_mat(b, _f32, False) for b in bs) \
+        and left_w.numel() == right_w.numel() == G * H * H and left_b.numel() == right_b.numel() == G * H \
+        and leaf_c_w.numel() == H * in_ and leaf_c_b.numel() == H \
+        and (not go or (leaf_o_w.numel() == H * in_ and leaf_o_b.numel() == H)), "treelstm_pack"
+    dev = left_w.device
+
+    def run(mode, w0, w1, b0, b1, shape, nb, g):
+        dst = torch.empty(shape, dtype=_bf16, device=dev)
+        bias = torch.empty(nb, dtype=_f32, device=dev) if nb else None
+        check(_lib().bigdl_treelstm_pack(C.c_int(mode), ptr(w0), ptr(w1), ptr(b0), ptr(b1), ptr(dst), ptr(bias),
+                                         C.c_int(H), C.c_int(in_), C.c_int(g), _ll(dst.numel()), _s()), "treelstm_pack")
+        return dst, bias
+    wc, bc = run(0, left_w, right_w, left_b, right_b, (G, H16, 2 * _up(H, 32)), G * H16, G)
+    wl, bl = run(1, leaf_c_w, leaf_o_w, leaf_c_b, leaf_o_b, (GL, H16, _up(in_, 32)), GL * H16, GL)
+    wt, _ = run(2, left_w, right_w, None, None, (2, H16, _up(G * Hp, 32)), 0, G)
+    wlt, _ = run(3, leaf_c_w, leaf_o_w, None, None, (_up(in_, 8), GL * Hp), 0, GL)
+    return {"go": go, "H": H, "in": in_, "wc": wc, "bc": bc, "wl": wl, "bl": bl, "wt": wt, "wlt": wlt}
+
+
+_TL_MODES = {"comp_fwd": 0, "leaf_fwd": 1, "comp_bwd": 2, "leaf_bwd": 3}
+
+
+def treelstm_level(mode, go, plan, row0, rows, H, in_, a, w, bias=None, c=None, h=None, act=None, tc=None, xs=None,
+                   gy=None, pact=None, pdc=None, dg=None, dc=None):
+    """One level launch of k_treelstm (``mode`` in comp_fwd, leaf_fwd, comp_bwd, leaf_bwd) over plan rows
+    ``[row0, row0 + rows)`` of the int32 plan ``[5][R]``.  ``c`` / ``h`` / ``gy`` are node-indexed [nodes][H];
+    ``act``, ``tc``, ``xs``, ``dg``, ``dc`` start at the level's first row; ``a`` is the gather source (h, the
+    embedding rows, or the composer gate gradients of all levels, with ``pact`` / ``pdc`` the composer saves
+    of all levels)."""
+    G, GL, Hp = (5 if go else 4), (2 if go else 1), _up(H, 8)
+    m = _TL_MODES[mode]
+    need = {"act": rows * (G if m in (0, 2) else 1) * H, "tc": rows * H, "dc": rows * H,
+            "xs": rows * (2 * Hp if m == 0 else _up(in_, 8)), "dg": rows * (G if m == 2 else GL) * Hp}
+    got = {"act": act, "tc": tc, "dc": dc, "xs": xs, "dg": dg}
+    assert treelstm_ok(H, in_, G) and plan.dtype == torch.int32 and plan.dim() == 2 and plan.shape[0] == 5 \
+        and plan.is_contiguous() and rows > 0 and rows % 32 == 0 and 0 <= row0 and row0 + rows <= plan.shape[1] \
+        and all(_tl_mat(t, _bf16) for t in (a, w, h, xs, gy, dg)) \
+        and all(_tl_mat(t, _f32) for t in (bias, c, act, tc, pact, pdc, dc)) \
+        and all(t is None or t.numel() >= need[k] for k, t in got.items()), f"treelstm_level[{mode}]"
+    check(_lib().bigdl_treelstm_level(C.c_int(m), C.c_int(1 if go else 0), ptr(plan), _ll(plan.shape[1]), _ll(row0),
+                                      C.c_int(rows), C.c_int(H), C.c_int(in_), ptr(a), ptr(w), ptr(bias), ptr(c), ptr(h),
+                                      ptr(act), ptr(tc), ptr(xs), ptr(gy), ptr(pact), ptr(pdc), ptr(dg), ptr(dc), _s()),
+          f"treelstm_level[{mode}]")
+
+
+def _tl_zeros(n, dtype, dev):
+    """n zeros through the native fill (n · element size is a multiple of 4 for every caller: H is even)."""
+    t = torch.empty(max(n, 8), dtype=dtype, device=dev)
+    assert zero_fill(t.view(torch.int32)) is not NotImplemented, "treelstm zero fill"
+    return t
+
+
+@register("treelstm_forward")
+def treelstm_forward(x, plan, pack, train=True):
+    """Every node's h of a planned batch: ``x`` [B·L][in] bf16 embeddings → (h [B·N][H] bf16 with zero rows for
+    padding nodes, state).  One leaf launch and one composer launch per tree height, looped in C++
+    (bigdl_treelstm_fwd).  ``state`` holds the fp32 saves for :func:`treelstm_backward` (None when ``train``
+    is false)."""
+    if not (isinstance(plan, dict) and isinstance(pack, dict) and _tl_mat(x, _bf16)) or x.dim() != 2 \
+            or tuple(x.shape) != (plan["B"] * plan["L"], pack["in"]):
+        return NotImplemented
+    go, H, in_, dev = pack["go"], pack["H"], pack["in"], x.device
+    G, Hp, R0, Rc = (5 if go else 4), _up(H, 8), plan["R0"], plan["R"] - plan["R0"]
+    nodes = plan["B"] * plan["N"]
+    h = _tl_zeros(nodes * H, _bf16, dev)[:nodes * H].view(nodes, H)
+    c = torch.empty(nodes * H, dtype=_f32, device=dev)
+    st = None
+    if train:
+        f = lambda n: torch.empty(max(n, 1), dtype=_f32, device=dev)  # noqa: E731
+        st = {"plan": plan, "c": c, "x": x, "act_l": f(R0 * H) if go else None, "tc_l": f(R0 * H),
+              "xs_l": _tl_zeros(R0 * _up(in_, 8), _bf16, dev), "act_c": f(Rc * G * H) if Rc else None,
+              "tc_c": f(Rc * H) if Rc else None, "xs_c": _tl_zeros(Rc * 2 * Hp, _bf16, dev) if Rc else None}
+    lvl = (C.c_int * len(plan["lvl"]))(*plan["lvl"])
+    g = (lambda k: ptr(st[k])) if train else (lambda k: ptr(None))
+    check(_lib().bigdl_treelstm_fwd(C.c_int(1 if go else 0), ptr(plan["plan"]), _ll(plan["R"]), lvl, C.c_int(len(plan["lvl"])),
+                                    C.c_int(H), C.c_int(in_), ptr(x), ptr(pack["wl"]), ptr(pack["bl"]), ptr(pack["wc"]),
+                                    ptr(pack["bc"]), ptr(c), ptr(h), g("act_l"), g("tc_l"), g("xs_l"), g("act_c"),
+                                    g("tc_c"), g("xs_c"), _s()), "treelstm_fwd")
+    return h, st
+
+
+@register("treelstm_backward")
+def treelstm_backward(gy, state, pack, grads=None, scale=1.0, need_input=True):
+    """Backward of :func:`treelstm_forward`: ``gy`` [B·N][H] bf16.  One launch per level from the roots down
+    (bigdl_treelstm_bwd), then one native GEMM per parameter group over all rows: ``grads`` maps the layer's
+    parameter names to their fp32 gradient tensors, which receive ``scale`` × the gradient through a padded
+    fp32 scratch and the strided accumulate kernel.  Returns the embedding gradient [B·L][in] bf16 (None
+    unless ``need_input``)."""
+    if not (isinstance(state, dict) and isinstance(pack, dict) and _tl_mat(gy, _bf16)):
+        return NotImplemented
+    plan, go, H, in_, dev = state["plan"], pack["go"], pack["H"], pack["in"], gy.device
+    G, GL, Hp, in8, R0 = (5 if go else 4), (2 if go else 1), _up(H, 8), _up(in_, 8), plan["R0"]
+    Rc = plan["R"] - R0
+    if gy.numel() != plan["B"] * plan["N"] * H:
+        return NotImplemented
+    dg_l = _tl_zeros(R0 * GL * Hp, _bf16, dev)[:R0 * GL * Hp].view(R0, GL * Hp)
+    dg_c = _tl_zeros(Rc * G * Hp, _bf16, dev)[:Rc * G * Hp].view(Rc, G * Hp) if Rc else None
+    dc_c = torch.empty(Rc * H, dtype=_f32, device=dev) if Rc else None
+    lvl = (C.c_int * len(plan["lvl"]))(*plan["lvl"])
+    check(_lib().bigdl_treelstm_bwd(C.c_int(1 if go else 0), ptr(plan["plan"]), _ll(plan["R"]), lvl, C.c_int(len(plan["lvl"])),
+                                    C.c_int(H), C.c_int(in_), ptr(gy), ptr(pack["wt"]), ptr(state["c"]), ptr(state["act_l"]),
+                                    ptr(state["tc_l"]), ptr(state["act_c"]), ptr(state["tc_c"]), ptr(dg_l), ptr(dg_c),
+                                    ptr(dc_c), _s()), "treelstm_bwd")
+
+    def acc(name, src, g, ncol, ld):
+        check(_lib().bigdl_treelstm_acc(ptr(grads[name]), C.c_void_p(src), C.c_int(g), C.c_int(H), C.c_int(ncol),
+                                        C.c_int(ld), _s()), "treelstm_acc")
+    if grads is not None and scale != 0:
+        assert all(_tl_mat(t, _f32, False) for t in grads.values()), "treelstm_backward: gradients"
+        # leaf: [(c, o)·H8][in8] = dg_lᵀ · the saved embedding rows; bias = column sums
+        gw = _tl_zeros(GL * Hp * in8, _f32, dev)
+        gb = _tl_zeros(GL * Hp, _f32, dev)
+        assert wgrad_rows(dg_l, state["xs_l"][:R0 * in8].view(R0, in8), gw, scale) is not NotImplemented \
+            and colsum_acc(dg_l, gb[:GL * Hp], scale) is not NotImplemented, "treelstm_backward: leaf gradients"
+        for k, nm in enumerate(("c", "o")[:GL]):
+            acc(f"leaf_{nm}_weight", gw.data_ptr() + 4 * k * Hp * in8, 1, in_, in8)
+            acc(f"leaf_{nm}_bias", gb.data_ptr() + 4 * k * Hp, 1, 1, 1)
+        if Rc:
+            # composer: [G·H8][lh | rh] = dg_cᵀ · the saved gathered rows: both weights in one GEMM
+            gw = _tl_zeros(G * Hp * 2 * Hp, _f32, dev)
+            gb = _tl_zeros(G * Hp, _f32, dev)
+            assert wgrad_rows(dg_c, state["xs_c"][:Rc * 2 * Hp].view(Rc, 2 * Hp), gw, scale) is not NotImplemented \
+                and colsum_acc(dg_c, gb[:G * Hp], scale) is not NotImplemented, "treelstm_backward: composer gradients"
+            for k, nm in enumerate(("left", "right")):
+                acc(f"{nm}_weight", gw.data_ptr() + 4 * k * Hp, G, H, 2 * Hp)
+                acc(f"{nm}_bias", gb.data_ptr(), G, 1, 1)
+    if not need_input:
+        return None
+    gx = gemm(dg_l, pack["wlt"])
+    assert gx is not NotImplemented, "treelstm_backward: embedding gradient"
+    return gx[:plan["B"] * plan["L"], :in_]
+
+
 # ---------------------------------------------------------------------------------- K13 ClassNLL
 def _nll_args(logp, target_1b, weights):
     lp = logp.unsqueeze(0) if logp.dim() == 1 else logp
