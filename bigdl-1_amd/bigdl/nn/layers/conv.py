@@ -742,6 +742,31 @@ class VolumetricFullConvolution(AutogradModule):
         return y if batched else y.squeeze(0)
 
 
+def _lc_native(layer, x_mem, geom, order):
+    """The locally connected layers on the per-location MFMA kernels (ops/csrc/locally_connected.hip):
+    ``x_mem`` is the input as NHWC memory (N, H, W, C), the result the output as NHWC memory (N, oH, oW, O) in
+    bf16, or None when the torch path serves the call.  Native: a GPU tensor, bf16 compute, the ops loaded,
+    C and O multiples of 8.  Every other case on a device is counted as a fallback of ``locally_connected``."""
+    if not x_mem.is_cuda:
+        return None
+    why = None
+    if not config.get_property("bigdl.lc.native") or not ops.native_has("lc_forward"):
+        why = "disabled"
+    elif Engine.compute_dtype() != torch.bfloat16 or not x_mem.is_floating_point() or x_mem.dtype == torch.float64:
+        why = "dtype"
+    elif geom[2] % 8 or geom[3] % 8:
+        why = "channels"
+    if why is None:
+        bias = layer.P("bias") if hasattr(layer, "bias") else None
+        y = ops.native_ops.locally_connected_autograd(x_mem.to(torch.bfloat16).contiguous(), layer.P("weight"),
+                                                      layer.cw("weight", torch.bfloat16), bias, geom, order)
+        if y is not NotImplemented:
+            return y
+        why = "geometry"
+    ops.native.note_fallback("locally_connected", why, (x_mem,))
+    return None
+
+
 class LocallyConnected2D(AutogradModule):
     """Unshared-weight 2-D conv (``LocallyConnected2D.scala``)."""
 
@@ -771,6 +796,13 @@ class LocallyConnected2D(AutogradModule):
         batched = x.dim() == 4
         if not batched:
             x = x.unsqueeze(0)
+        if x.is_cuda:
+            # (N, H, W, C) view: already NHWC memory for the NHWC format and for channels_last device activations
+            geom = (x.shape[2], x.shape[3], self.nIn, self.nOut, self.kH, self.kW, self.sH, self.sW, self.pH, self.pW)
+            y = _lc_native(self, x.permute(0, 2, 3, 1), geom, "CT")
+            if y is not None:
+                y = y if nhwc else y.permute(0, 3, 1, 2)
+                return y if batched else y.squeeze(0)
         cols = F.unfold(x, (self.kH, self.kW), padding=(self.pH, self.pW), stride=(self.sH, self.sW))  # N, CKK, L
         y = torch.einsum("ncl,loc->nol", cols, self.P("weight").to(x.dtype))
         if self.withBias:
@@ -798,6 +830,13 @@ class LocallyConnected1D(AutogradModule):
         batched = x.dim() == 3
         if not batched:
             x = x.unsqueeze(0)
+        if x.is_cuda:
+            # (N, T, F) frames are the NHWC image (N, F, 1, T); the weight's K order (kx, f) is NHWC's own
+            geom = (1, x.shape[1], self.inSize, self.outSize, 1, self.kW, 1, self.sW, 0, 0)
+            y = _lc_native(self, x.unsqueeze(1), geom, "TC")
+            if y is not None:
+                y = y.squeeze(1)
+                return y if batched else y.squeeze(0)
         win = x.unfold(1, self.kW, self.sW)  # N, L, F, kW
         win = win.permute(0, 1, 3, 2).reshape(x.shape[0], self.nOutFrame, -1)
         y = torch.einsum("nlc,loc->nlo", win, self.P("weight").to(x.dtype)) + self.P("bias").to(x.dtype)

@@ -3841,6 +3841,164 @@ def treelstm_backward(gy, state, pack, grads=None, scale=1.0, need_input=True):
     return gx[:plan["B"] * plan["L"], :in_]
 
 
+# ------------------------------------------------------------------- LocallyConnected (locally_connected.hip)
+# geom = (H, W, C, O, kH, kW, sH, sW, pH, pW); order "CT": K runs (c, ky, kx) (LocallyConnected2D), "TC": (kx, c)
+# (LocallyConnected1D).  Activations are NHWC memory: x [N][H][W][C], y / gy [N][oH][oW][O].
+_LC_ORDER = {"CT": 0, "TC": 1}
+
+
+def _lc_ints(geom):
+    return [C.c_int(int(v)) for v in geom]
+
+
+def lc_out_hw(geom):
+    H, W, _, _, kH, kW, sH, sW, pH, pW = geom
+    return (H + 2 * pH - kH) // sH + 1, (W + 2 * pW - kW) // sW + 1
+
+
+def lc_wd_numel(geom) -> int:
+    """Elements of the data gradient's transposed weights [H·W][C][slots][O]; 0 when the kernels do not take
+    the geometry (C, O multiples of 8, at most 256 taps, at most 65535 locations and pixels)."""
+    l = _lib()
+    if l is None or not hasattr(l, "bigdl_lc_wd_numel") or len(geom) != 10 or min(geom[:8]) <= 0 or min(geom[8:]) < 0:
+        return 0
+    l.bigdl_lc_wd_numel.restype = C.c_longlong
+    return int(l.bigdl_lc_wd_numel(*_lc_ints(geom)))
+
+
+def _lc_t(t, dtype, numel):
+    return t.is_cuda and t.dtype == dtype and t.is_contiguous() and _al16(t) and t.numel() == numel
+
+
+def _lc_sizes(geom):
+    H, W, C_, O, kH, kW = geom[:6]
+    oH, oW = lc_out_hw(geom)
+    return H * W, oH * oW, C_ * kH * kW
+
+
+@register("lc_forward")
+def lc_forward(x, w, bias, geom, order="CT", out=None):
+    """y [N][oH][oW][O] bf16 = the per-location product of x [N][H][W][C] bf16 with w [L][O][K] bf16, plus the
+    fp32 bias [L][O] (or None): k_lc_gemm."""
+    if lc_wd_numel(geom) <= 0:
+        return NotImplemented
+    P_, L, K = _lc_sizes(geom)
+    C_, O, N_ = geom[2], geom[3], x.shape[0]
+    oH, oW = lc_out_hw(geom)
+    y = out if out is not None else torch.empty((N_, oH, oW, O), dtype=_bf16, device=x.device)
+    assert N_ > 0 and _lc_t(x, _bf16, N_ * P_ * C_) and _lc_t(w, _bf16, L * O * K) and _lc_t(y, _bf16, N_ * L * O) \
+        and (bias is None or _lc_t(bias, _f32, L * O)), "lc_forward"
+    check(_lib().bigdl_lc_forward(C.c_int(_LC_ORDER[order]), ptr(x), ptr(w), ptr(bias), ptr(y), C.c_int(N_),
+                                  *_lc_ints(geom), _s()), "lc_forward")
+    return y
+
+
+@register("lc_weight_transpose")
+def lc_weight_transpose(w, geom, order="CT", out=None):
+    """Wd [H·W][C][slots][O] bf16 = w [L][O][K] regrouped by input pixel for :func:`lc_dgrad` (k_lc_wt); slots
+    that no location reaches are zero."""
+    n = lc_wd_numel(geom)
+    if n <= 0:
+        return NotImplemented
+    P_, L, K = _lc_sizes(geom)
+    wd = out if out is not None else torch.empty(n, dtype=_bf16, device=w.device)
+    assert _lc_t(w, _bf16, L * geom[3] * K) and _lc_t(wd, _bf16, n), "lc_weight_transpose"
+    check(_lib().bigdl_lc_weight_transpose(C.c_int(_LC_ORDER[order]), ptr(w), ptr(wd), *_lc_ints(geom), _s()),
+          "lc_weight_transpose")
+    return wd
+
+
+@register("lc_dgrad")
+def lc_dgrad(gy, wd, geom, N_, out=None):
+    """gx [N][H][W][C] bf16 from gy [N][oH][oW][O] bf16 and the transposed weights: the TC body of k_lc_gemm
+    over input pixels.  No atomics: the same bits on every run."""
+    n = lc_wd_numel(geom)
+    if n <= 0:
+        return NotImplemented
+    H, W, C_, O = geom[:4]
+    P_, L, _ = _lc_sizes(geom)
+    gx = out if out is not None else torch.empty((N_, H, W, C_), dtype=_bf16, device=gy.device)
+    assert N_ > 0 and _lc_t(gy, _bf16, N_ * L * O) and _lc_t(wd, _bf16, n) and _lc_t(gx, _bf16, N_ * P_ * C_), "lc_dgrad"
+    check(_lib().bigdl_lc_dgrad(ptr(gy), ptr(wd), ptr(gx), C.c_int(N_), *_lc_ints(geom), _s()), "lc_dgrad")
+    return gx
+
+
+@register("lc_wgrad")
+def lc_wgrad(x, gy, geom, order="CT", scale=1.0, out=None):
+    """gw [L][O][K] fp32 = scale · Σ_n gy[n,l,o] · patch_l[n,k] in the layer's own order (k_lc_wgrad): each
+    element is written once by the one block that sums all batch rows, so the result is bit-reproducible."""
+    if lc_wd_numel(geom) <= 0:
+        return NotImplemented
+    P_, L, K = _lc_sizes(geom)
+    C_, O, N_ = geom[2], geom[3], x.shape[0]
+    gw = out if out is not None else torch.empty((L, O, K), dtype=_f32, device=x.device)
+    assert N_ > 0 and _lc_t(x, _bf16, N_ * P_ * C_) and _lc_t(gy, _bf16, N_ * L * O) and gw.is_cuda and gw.dtype == _f32 \
+        and gw.is_contiguous() and gw.numel() == L * O * K, "lc_wgrad"
+    check(_lib().bigdl_lc_wgrad(C.c_int(_LC_ORDER[order]), ptr(x), ptr(gy), ptr(gw), _f(scale), C.c_int(N_),
+                                *_lc_ints(geom), _s()), "lc_wgrad")
+    return gw
+
+
+_LC_WD: dict = {}   # (weight address, geom, order) → (generation, weakref(weight), Wd)
+
+
+def _lc_wd_cached(wb, geom, order):
+    """The transposed weights of ``wb``, rebuilt when the weights changed: an arena shadow is keyed by the
+    arena's shadow generation (optimizer kernels write it behind torch's version counter), any other tensor
+    by its version."""
+    import weakref
+    arena = _shadow_arena(wb)
+    gen = ("arena", arena.shadow_gen) if arena is not None else ("version", wb._version)
+    key = (wb.data_ptr(), geom, order)
+    c = _LC_WD.get(key)
+    if c is None or c[0] != gen or c[1]() is not wb:
+        for k in [k for k, v in _LC_WD.items() if v[1]() is None]:
+            del _LC_WD[k]
+        c = _LC_WD[key] = (gen, weakref.ref(wb), lc_weight_transpose(wb, geom, order))
+    return c[2]
+
+
+class _LocallyConnectedFn(torch.autograd.Function):
+    """The locally connected layers as one autograd op on NHWC memory: ``w`` is the fp32 parameter (it
+    receives the gradient), ``wb`` its bf16 shadow, which is what the kernels read."""
+
+    @staticmethod
+    def forward(ctx, x, w, wb, b, geom, order):
+        bias = b.detach().float().contiguous() if b is not None else None
+        y = lc_forward(x, wb, bias, geom, order)
+        ctx.save_for_backward(x)
+        ctx.wb = wb   # the very tensor object: the transposed-weight cache keys on it
+        ctx.cfg = (geom, order, w.dtype, b.dtype if b is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,), wb = ctx.saved_tensors, ctx.wb
+        geom, order, wdt, bdt = ctx.cfg
+        gy = gy.to(_bf16).contiguous()
+        N_, L, O = x.shape[0], gy.shape[1] * gy.shape[2], gy.shape[3]
+        gx = lc_dgrad(gy, _lc_wd_cached(wb, geom, order), geom, N_) if ctx.needs_input_grad[0] else None
+        gw = lc_wgrad(x, gy, geom, order).view(wb.shape).to(wdt) if ctx.needs_input_grad[1] else None
+        gb = None
+        if bdt is not None and ctx.needs_input_grad[3]:
+            gb = torch.zeros(L * O, dtype=_f32, device=gy.device)
+            assert colsum_acc(gy.view(N_, L * O), gb) is not NotImplemented, "locally connected bias gradient"
+            gb = gb.view(L, O).to(bdt)
+        return gx, gw, None, gb, None, None
+
+
+def locally_connected_autograd(x, w, wb, b, geom, order="CT"):
+    """Differentiable native locally connected layer: x [N][H][W][C] bf16 contiguous → y [N][oH][oW][O] bf16
+    (NotImplemented when the kernels do not take the geometry or the operands)."""
+    geom = tuple(int(v) for v in geom)
+    P_, L, K = _lc_sizes(geom)
+    if lc_wd_numel(geom) <= 0 or x.dim() != 4 or tuple(x.shape[1:]) != (geom[0], geom[1], geom[2]) or x.shape[0] <= 0 \
+            or not (_lc_t(x, _bf16, x.numel()) and _lc_t(wb, _bf16, L * geom[3] * K) and w.numel() == wb.numel()) \
+            or (b is not None and b.numel() != L * geom[3]):
+        return NotImplemented
+    return _LocallyConnectedFn.apply(x, w, wb, b, geom, order)
+
+
 # ---------------------------------------------------------------------------------- K13 ClassNLL
 def _nll_args(logp, target_1b, weights):
     lp = logp.unsqueeze(0) if logp.dim() == 1 else logp
