@@ -167,7 +167,38 @@ class Bilinear(AutogradModule):
         if bias_res:
             RandomUniform(-stdv, stdv).init(self.bias)
 
+    def _native(self, x1, x2):
+        """The fused MFMA kernels (ops/csrc/bilinear.hip) as one autograd op, or None when the torch path serves
+        the call.  Native: 2-D GPU inputs of equal batch ≥ 1, bf16 compute, the ops loaded, both input sizes
+        multiples of 8.  Every other case on a device is counted as a fallback of ``bilinear``.  The native path
+        casts fp32 / fp16 inputs to bf16 and returns bf16 whatever their dtype, as the other native layers do."""
+        from ...utils import config
+        from ...utils.engine import Engine
+        why = None
+        if not config.get_property("bigdl.bilinear.native") or not ops.native_has("bilinear_forward"):
+            why = "disabled"
+        elif Engine.compute_dtype() != torch.bfloat16 or any(not t.is_floating_point() or t.dtype == torch.float64
+                                                             for t in (x1, x2)):
+            why = "dtype"
+        elif x1.dim() != 2 or x2.dim() != 2 or x1.shape[0] != x2.shape[0] or x1.shape[0] < 1 or not x2.is_cuda:
+            why = "shape"
+        elif x1.shape[1] % 8 or x2.shape[1] % 8:
+            why = "geometry"
+        if why is None:
+            y = ops.native_ops.bilinear_autograd(x1.to(torch.bfloat16).contiguous(), x2.to(torch.bfloat16).contiguous(),
+                                                 self.P("weight"), self.cw("weight", torch.bfloat16),
+                                                 self.P("bias") if self.biasRes else None)
+            if y is not NotImplemented:
+                return y
+            why = "geometry"
+        ops.native.note_fallback("bilinear", why, (x1, x2))
+        return None
+
     def _forward(self, x):
+        if x[1].is_cuda:
+            y = self._native(x[1], x[2])
+            if y is not None:
+                return y
         return F.bilinear(x[1], x[2], self.P("weight").to(x[1].dtype),
                           self.P("bias").to(x[1].dtype) if self.biasRes else None)
 

@@ -16,6 +16,7 @@ static const char* kOps[] = {
     "convlstm_step", "convlstm_seq_fwd", "convlstm_seq_bwd", "convlstm_peephole_grad",
     "treelstm_level", "treelstm_fwd", "treelstm_bwd", "treelstm_pack",
     "lc_forward", "lc_dgrad", "lc_wgrad", "lc_weight_transpose",
+    "bilinear_forward", "bilinear_gx", "bilinear_wgrad",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

@@ -3999,6 +3999,114 @@ def locally_connected_autograd(x, w, wb, b, geom, order="CT"):
     return _LocallyConnectedFn.apply(x, w, wb, b, geom, order)
 
 
+# ------------------------------------------------------------------------------------ Bilinear (bilinear.hip)
+# x1 [B][I], x2 [B][J], w [K][I][J], y / gy [B][K]; I and J multiples of 8 (16-byte rows), any K ≥ 1.
+def _bil_t(t, dtype, shape):
+    return t.is_cuda and t.dtype == dtype and t.is_contiguous() and _al16(t) and tuple(t.shape) == tuple(shape)
+
+
+def _bil_vec(t, K):
+    """None or a dense fp32 device vector [K]: the kernels access it by scalars, so 4-byte alignment is enough (a
+    parameter may be a slice of a flat arena)."""
+    return t is None or (t.is_cuda and t.dtype == _f32 and t.is_contiguous() and tuple(t.shape) == (K,))
+
+
+def _bil_takes(B, I, J, K):
+    return B > 0 and K > 0 and I > 0 and J > 0 and I % 8 == 0 and J % 8 == 0 and K <= 65535 and I <= 65535 * 16 \
+        and J <= 65535 * 64
+
+
+@register("bilinear_forward")
+def bilinear_forward(x1, x2, w, bias=None, out=None):
+    """y [B][K] bf16 = x1ᵀ·W[k]·x2 + bias[k] (fp32 bias or None): k_bil_u, U_k = x2·W[k]ᵀ on the MFMA, times x1
+    and summed over i on the accumulators."""
+    (B, I), J, K = x1.shape, x2.shape[1], w.shape[0]
+    if not _bil_takes(B, I, J, K):
+        return NotImplemented
+    y = out if out is not None else torch.empty((B, K), dtype=_bf16, device=x1.device)
+    assert _bil_t(x1, _bf16, (B, I)) and _bil_t(x2, _bf16, (B, J)) and _bil_t(w, _bf16, (K, I, J)) \
+        and _bil_t(y, _bf16, (B, K)) and _bil_vec(bias, K), "bilinear_forward"
+    check(_lib().bigdl_bilinear_forward(ptr(x1), ptr(x2), ptr(w), ptr(bias), ptr(y), C.c_int(B), C.c_int(I), C.c_int(J),
+                                        C.c_int(K), _s()), "bilinear_forward")
+    return y
+
+
+@register("bilinear_gx")
+def bilinear_gx(which, gy, xo, w, out=None):
+    """which = 1: gx1 [B][I] bf16 = Σ_k gy[b,k]·(W[k]·x2[b]), ``xo`` = x2 (k_bil_u); which = 2: gx2 [B][J] =
+    Σ_k gy[b,k]·(W[k]ᵀ·x1[b]), ``xo`` = x1 (k_bil_v, W read transposed from LDS).  No atomics."""
+    K, I, J = w.shape
+    B = gy.shape[0]
+    if which not in (1, 2) or not _bil_takes(B, I, J, K):
+        return NotImplemented
+    n_in, n_out = (J, I) if which == 1 else (I, J)
+    gx = out if out is not None else torch.empty((B, n_out), dtype=_bf16, device=gy.device)
+    assert _bil_t(gy, _bf16, (B, K)) and _bil_t(xo, _bf16, (B, n_in)) and _bil_t(w, _bf16, (K, I, J)) \
+        and _bil_t(gx, _bf16, (B, n_out)), "bilinear_gx"
+    check(_lib().bigdl_bilinear_gx(C.c_int(which), ptr(gy), ptr(xo), ptr(w), ptr(gx), C.c_int(B), C.c_int(I), C.c_int(J),
+                                   C.c_int(K), _s()), "bilinear_gx")
+    return gx
+
+
+@register("bilinear_wgrad")
+def bilinear_wgrad(gy, x1, x2, scale=1.0, out=None, out_bias=None):
+    """gw [K][I][J] fp32 = scale · Σ_b gy[b,k]·x1[b,i]·x2[b,j] (k_bil_wgrad: one block sums all batch rows of its
+    tile, the product gy·x1 split exactly into two bf16 terms, so each element is written once).  ``out_bias``
+    [K] fp32, when given, receives scale · Σ_b gy[b,k] from the same launch."""
+    (B, K), I, J = gy.shape, x1.shape[1], x2.shape[1]
+    if not _bil_takes(B, I, J, K):
+        return NotImplemented
+    gw = out if out is not None else torch.empty((K, I, J), dtype=_f32, device=gy.device)
+    assert _bil_t(gy, _bf16, (B, K)) and _bil_t(x1, _bf16, (B, I)) and _bil_t(x2, _bf16, (B, J)) \
+        and _bil_t(gw, _f32, (K, I, J)) and _bil_vec(out_bias, K), "bilinear_wgrad"
+    check(_lib().bigdl_bilinear_wgrad(ptr(gy), ptr(x1), ptr(x2), ptr(gw), ptr(out_bias), _f(scale), C.c_int(B),
+                                      C.c_int(I), C.c_int(J), C.c_int(K), _s()), "bilinear_wgrad")
+    return gw
+
+
+class _BilinearFn(torch.autograd.Function):
+    """Bilinear as one autograd op: ``w`` is the fp32 parameter (it receives the gradient), ``wb`` its bf16
+    shadow, which is what the kernels read."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w, wb, b):
+        bias = b.detach().float().contiguous() if b is not None else None
+        y = bilinear_forward(x1, x2, wb, bias)
+        ctx.save_for_backward(x1, x2)
+        ctx.wb = wb   # a shadow the optimizer kernels write behind torch's version counter: not a saved tensor
+        ctx.cfg = (w.dtype, b.dtype if b is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x1, x2), wb = ctx.saved_tensors, ctx.wb
+        wdt, bdt = ctx.cfg
+        gy = gy.to(_bf16).contiguous()
+        need = ctx.needs_input_grad
+        gx1 = bilinear_gx(1, gy, x2, wb) if need[0] else None
+        gx2 = bilinear_gx(2, gy, x1, wb) if need[1] else None
+        gw = gb = None
+        if need[2] or (bdt is not None and need[4]):
+            gb = torch.empty(wb.shape[0], dtype=_f32, device=gy.device) if bdt is not None and need[4] else None
+            gw = bilinear_wgrad(gy, x1, x2, out_bias=gb)
+            gw = gw.to(wdt) if need[2] else None
+            gb = gb.to(bdt) if gb is not None else None
+        return gx1, gx2, gw, None, gb
+
+
+def bilinear_autograd(x1, x2, w, wb, b):
+    """Differentiable native Bilinear: x1 [B][I], x2 [B][J] bf16 contiguous → y [B][K] bf16 (NotImplemented when
+    the kernels do not take the sizes or the operands)."""
+    if x1.dim() != 2 or x2.dim() != 2 or wb.dim() != 3 or x1.shape[0] != x2.shape[0]:
+        return NotImplemented
+    (B, I), J, K = x1.shape, x2.shape[1], wb.shape[0]
+    if not _bil_takes(B, I, J, K) or not (_bil_t(x1, _bf16, (B, I)) and _bil_t(x2, _bf16, (B, J))
+                                          and _bil_t(wb, _bf16, (K, I, J)) and tuple(w.shape) == (K, I, J)) \
+            or (b is not None and b.numel() != K):
+        return NotImplemented
+    return _BilinearFn.apply(x1, x2, w, wb, b)
+
+
 # ---------------------------------------------------------------------------------- K13 ClassNLL
 def _nll_args(logp, target_1b, weights):
     lp = logp.unsqueeze(0) if logp.dim() == 1 else logp
