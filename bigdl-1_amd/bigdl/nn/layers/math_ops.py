@@ -284,7 +284,48 @@ class Highway(AutogradModule):
                 self.bias[:size].fill_(-1.0)  # carry bias (transform gate starts closed)
                 self.bias[size:].zero_()
 
+    # the names ``_forward`` maps, as the kernels' activation
+    _NATIVE_ACT = {"tanh": "tanh", "Tanh": "tanh", "relu": "relu", "ReLU": "relu", "sigmoid": "sigmoid",
+                   "Sigmoid": "sigmoid"}
+
+    def _native(self, x):
+        """The fused MFMA kernels (ops/csrc/highway.hip) as one autograd op, or None when the torch path serves the
+        call.  Native: a 2-D GPU input [B][size] with B ≥ 1, bf16 compute, the ops loaded, size a multiple of 8,
+        no activation or one of the names ``_forward`` maps.  Every other case on a device is counted as a
+        fallback of ``highway``.  The native path casts fp32 / fp16 inputs to bf16 and returns bf16 whatever
+        their dtype, as the other native layers do."""
+        from ... import ops
+        from ...utils import config
+        from ...utils.engine import Engine
+        act, why = "identity", None
+        if self.activation is not None:
+            name = self.activation if isinstance(self.activation, str) else type(self.activation).__name__
+            act = self._NATIVE_ACT.get(name)
+        if not config.get_property("bigdl.highway.native") or not ops.native_has("highway_forward"):
+            why = "disabled"
+        elif Engine.compute_dtype() != torch.bfloat16 or not x.is_floating_point() or x.dtype == torch.float64:
+            why = "dtype"
+        elif x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != self.size:
+            why = "shape"
+        elif self.size % 8:
+            why = "geometry"
+        elif act is None:
+            why = "activation"
+        if why is None:
+            y = ops.native_ops.highway_autograd(x.to(torch.bfloat16).contiguous(), self.P("weight"),
+                                                self.cw("weight", torch.bfloat16),
+                                                self.P("bias") if self.withBias else None, act)
+            if y is not NotImplemented:
+                return y
+            why = "geometry"
+        ops.native.note_fallback("highway", why, (x,))
+        return None
+
     def _forward(self, x):
+        if x.is_cuda:
+            y = self._native(x)
+            if y is not None:
+                return y
         w = self.P("weight").to(x.dtype)
         y = x @ w.t()
         if self.withBias:

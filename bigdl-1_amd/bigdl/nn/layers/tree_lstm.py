@@ -245,9 +245,18 @@ class BinaryTreeLSTM(TreeLSTM):
         pack = self._nat_pack()
         h, st = NO.treelstm_forward(x.reshape(B * L, -1).to(torch.bfloat16).contiguous(), plan, pack, self.train)
         if self.train:
-            self._nat = (id(input), st, pack)
+            self._nat = ((input[1], input[2]), st, pack)
         self._gi_done = False
         return h.view(B, plan["N"], self.hiddenSize).to(x.dtype)
+
+    def _nat_of(self, input):
+        """The native forward's saves when ``input`` holds the tensors that forward saw, else None.  The tensors
+        themselves are compared, not the Table around them: a caller may wrap them in a new Table for the
+        backward, and the id of the forward's Table, once freed, may or may not be handed out again."""
+        nat = getattr(self, "_nat", None)
+        if nat is not None and isinstance(input, Table) and input.get(1) is nat[0][0] and input.get(2) is nat[0][1]:
+            return nat
+        return None
 
     def _nat_backward(self, input, gradOutput, need_input):
         from ...ops import native_ops as NO
@@ -266,7 +275,7 @@ class BinaryTreeLSTM(TreeLSTM):
         return Table(gx.reshape(x.shape).to(x.dtype), torch.zeros_like(input[2]))
 
     def updateGradInput(self, input, gradOutput):
-        if getattr(self, "_nat", None) is not None and self._nat[0] == id(input):
+        if self._nat_of(input) is not None:
             return self._nat_backward(input, gradOutput, True)
         gi = super().updateGradInput(input, gradOutput)
         if isinstance(gi, Table) and gi.get(2) is None:
@@ -277,7 +286,7 @@ class BinaryTreeLSTM(TreeLSTM):
         if getattr(self, "_gi_done", False):
             self._gi_done = False
             return
-        if getattr(self, "_nat", None) is not None and self._nat[0] == id(input):
+        if self._nat_of(input) is not None:
             self._nat_backward(input, gradOutput, False)
             self._gi_done = False
             return

@@ -17,6 +17,7 @@ static const char* kOps[] = {
     "treelstm_level", "treelstm_fwd", "treelstm_bwd", "treelstm_pack",
     "lc_forward", "lc_dgrad", "lc_wgrad", "lc_weight_transpose",
     "bilinear_forward", "bilinear_gx", "bilinear_wgrad",
+    "highway_forward", "highway_backward", "highway_wgrad",
 };
 
 extern "C" __attribute__((visibility("default"))) int bigdl_num_ops() {

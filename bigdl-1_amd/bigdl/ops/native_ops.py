@@ -4107,6 +4107,112 @@ def bilinear_autograd(x1, x2, w, wb, b):
     return _BilinearFn.apply(x1, x2, w, wb, b)
 
 
+# -------------------------------------------------------------------------------------- Highway (highway.hip)
+# x / y / gy / gx [B][N], w [2N][N] (rows 0..N-1 the transform gate, N..2N-1 the candidate), gates / dg [B][2N];
+# N a multiple of 8 (16-byte rows), any B ≥ 1.
+_HW_ACT = {"identity": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
+
+
+def _hw_takes(B, N):
+    return B > 0 and N > 0 and N % 8 == 0 and N <= 65535 * 32
+
+
+@register("highway_forward")
+def highway_forward(x, w, bias, act, gates=None, out=None):
+    """y [B][N] bf16 = t·h + (1−t)·x, t = σ(x·Wtᵀ + bt), h = act(x·Whᵀ + bh) (fp32 bias [2N] or None): k_hw_fwd,
+    both pre-activations of a column on the MFMA accumulators of one lane, y rounded once.  ``gates`` [B][2N]
+    bf16, when given (training), receives [t | h]; nothing else is written."""
+    B, N = x.shape
+    if act not in _HW_ACT or not _hw_takes(B, N):
+        return NotImplemented
+    y = out if out is not None else torch.empty((B, N), dtype=_bf16, device=x.device)
+    assert _bil_t(x, _bf16, (B, N)) and _bil_t(w, _bf16, (2 * N, N)) and _bil_t(y, _bf16, (B, N)) \
+        and (gates is None or _bil_t(gates, _bf16, (B, 2 * N))) and _bil_vec(bias, 2 * N), "highway_forward"
+    check(_lib().bigdl_highway_forward(ptr(x), ptr(w), ptr(bias), ptr(y), ptr(gates), C.c_int(B), C.c_int(N),
+                                       C.c_int(_HW_ACT[act]), _s()), "highway_forward")
+    return y
+
+
+@register("highway_backward")
+def highway_backward(gy, x, gates, w, act, need_input=True, out=None, out_dg=None):
+    """→ (gx, dg): dg [B][2N] bf16 = [gy·(h−x)·t(1−t) | gy·t·act'(h)] from the stored gates, and with
+    ``need_input`` gx [B][N] bf16 = dg·W + gy·(1−t) (else None), one launch (k_hw_bwd: dg formed chunk by chunk in
+    LDS as the GEMM's operand, W read transposed from LDS).  No atomics."""
+    B, N = gy.shape
+    if act not in _HW_ACT or not _hw_takes(B, N):
+        return NotImplemented
+    dg = out_dg if out_dg is not None else torch.empty((B, 2 * N), dtype=_bf16, device=gy.device)
+    gx = None
+    if need_input:
+        gx = out if out is not None else torch.empty((B, N), dtype=_bf16, device=gy.device)
+        assert _bil_t(w, _bf16, (2 * N, N)) and _bil_t(gx, _bf16, (B, N)), "highway_backward"
+    assert _bil_t(gy, _bf16, (B, N)) and _bil_t(x, _bf16, (B, N)) and _bil_t(gates, _bf16, (B, 2 * N)) \
+        and _bil_t(dg, _bf16, (B, 2 * N)), "highway_backward"
+    # without need_input the kernel reads no w and writes no gx: ``out`` is passed on only to be left as it is
+    check(_lib().bigdl_highway_backward(ptr(gy), ptr(x), ptr(gates), ptr(w), ptr(gx if need_input else out), ptr(dg),
+                                        C.c_int(B), C.c_int(N), C.c_int(_HW_ACT[act]), C.c_int(int(bool(need_input))),
+                                        _s()), "highway_backward")
+    return gx, dg
+
+
+@register("highway_wgrad")
+def highway_wgrad(dg, x, scale=1.0, out=None, out_bias=None):
+    """gw [2N][N] fp32 = scale · dgᵀ·x (k_hw_wgrad: one block sums all batch rows of its tile, so each element is
+    written once).  ``out_bias`` [2N] fp32, when given, receives scale · Σ_b dg[b] from the same launch."""
+    B, N = x.shape
+    if not _hw_takes(B, N):
+        return NotImplemented
+    gw = out if out is not None else torch.empty((2 * N, N), dtype=_f32, device=x.device)
+    assert _bil_t(dg, _bf16, (B, 2 * N)) and _bil_t(x, _bf16, (B, N)) and _bil_t(gw, _f32, (2 * N, N)) \
+        and _bil_vec(out_bias, 2 * N), "highway_wgrad"
+    check(_lib().bigdl_highway_wgrad(ptr(dg), ptr(x), ptr(gw), ptr(out_bias), _f(scale), C.c_int(B), C.c_int(N), _s()),
+          "highway_wgrad")
+    return gw
+
+
+class _HighwayFn(torch.autograd.Function):
+    """Highway as one autograd op: ``w`` is the fp32 parameter (it receives the gradient), ``wb`` its bf16
+    shadow, which is what the kernels read.  The gates are stored only when a gradient will be asked for."""
+
+    @staticmethod
+    def forward(ctx, x, w, wb, b, act):
+        bias = b.detach().float().contiguous() if b is not None else None
+        train = any(ctx.needs_input_grad)
+        gates = torch.empty((x.shape[0], 2 * x.shape[1]), dtype=_bf16, device=x.device) if train else None
+        y = highway_forward(x, wb, bias, act, gates=gates)
+        if train:
+            ctx.save_for_backward(x, gates)
+        ctx.wb = wb   # a shadow the optimizer kernels write behind torch's version counter: not a saved tensor
+        ctx.cfg = (act, w.dtype, b.dtype if b is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x, gates), wb = ctx.saved_tensors, ctx.wb
+        act, wdt, bdt = ctx.cfg
+        need = ctx.needs_input_grad
+        gx, dg = highway_backward(gy.to(_bf16).contiguous(), x, gates, wb, act, need_input=need[0])
+        gw = gb = None
+        if need[1] or (bdt is not None and need[3]):
+            gb = torch.empty(wb.shape[0], dtype=_f32, device=gy.device) if bdt is not None and need[3] else None
+            gw = highway_wgrad(dg, x, out_bias=gb)
+            gw = gw.to(wdt) if need[1] else None
+            gb = gb.to(bdt) if gb is not None else None
+        return gx, gw, None, gb, None
+
+
+def highway_autograd(x, w, wb, b, act):
+    """Differentiable native Highway: x [B][N] bf16 contiguous → y [B][N] bf16; ``act`` one of identity, tanh,
+    relu, sigmoid (NotImplemented when the kernels do not take the sizes or the operands)."""
+    if x.dim() != 2 or wb.dim() != 2 or act not in _HW_ACT:
+        return NotImplemented
+    B, N = x.shape
+    if not _hw_takes(B, N) or not (_bil_t(x, _bf16, (B, N)) and _bil_t(wb, _bf16, (2 * N, N))
+                                   and tuple(w.shape) == (2 * N, N)) or (b is not None and b.numel() != 2 * N):
+        return NotImplemented
+    return _HighwayFn.apply(x, w, wb, b, act)
+
+
 # ---------------------------------------------------------------------------------- K13 ClassNLL
 def _nll_args(logp, target_1b, weights):
     lp = logp.unsqueeze(0) if logp.dim() == 1 else logp

@@ -60,6 +60,7 @@ _REGISTRY = {
     "bigdl.rnn.nativeConvLSTM": (bool, True, "Recurrent(ConvLSTMPeephole) (2-D, stride 1, same padding, default activations, bf16 on a GPU) runs the fused conv-recurrent step kernels (convlstm.hip) with explicit BPTT; false = the generic per-step autograd path"),
     "bigdl.treelstm.native": (bool, True, "BinaryTreeLSTM on a GPU in bf16 (even hidden and input sizes, binary trees whose nodes have one parent) runs the fused gather-GEMM-gate level kernels (treelstm.hip) with an explicit level-reversed backward; false = the torch level-batched autograd path"),
     "bigdl.lc.native": (bool, True, "LocallyConnected2D / LocallyConnected1D on a GPU in bf16 (input and output channels multiples of 8) run the per-location MFMA kernels (locally_connected.hip) with an explicit data and weight gradient; false = the torch unfold + einsum autograd path"),
+    "bigdl.highway.native": (bool, True, "Highway on a GPU in bf16 (2-D input, size a multiple of 8, activation none / tanh / relu / sigmoid) runs the fused MFMA gate kernels (highway.hip) with explicit input, weight and bias gradients; false = the torch matmul + elementwise autograd path"),
     "bigdl.bilinear.native": (bool, True, "Bilinear on a GPU in bf16 (2-D inputs, both input sizes multiples of 8) runs the fused MFMA kernels (bilinear.hip) with explicit input and weight gradients; false = the torch F.bilinear autograd path"),
     "bigdl.checkpoint.async": (bool, True, "trigger-driven checkpoints: host snapshot on the training thread, serialise + write on a writer thread"),
     "bigdl.predict.compiled": (bool, True, "LocalPredictor / Predictor / PredictionService on a GPU: lower the model through the IR (BN fold, conv+sum+ReLU), plan each batch shape once and replay its forward as a HIP graph (the reference's predictors always convert, LocalPredictor.scala:66)"),
